@@ -3,6 +3,10 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches one rank per
 GPU with torch.distributed.run.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = milliseconds of one timed step, the
+schedule, `roofline.step` from that time).  `--full` adds everything else below - per-kernel events and the kernel roofline, the copy-rate
+probe, the long run and the other schedules, the uncompressed exchange, `cpu_baseline` with the oracle parity spot check, the plugin path,
+`configs`, the presets, protocol 2.  `--dump-outputs DIR` writes what the last timed step left for its caller (report.dump_outputs).
 
 Workload (BASELINE.json configs[2], SURVEY.md §8d "Config 3"): one denoise step of FLUX.1-dev 1024^2 under
 ring-attention sequence parallelism of logical degree 8 with the 1-bit residual codec, as seen by ONE rank:
@@ -81,7 +85,7 @@ def main():
     #   schedules.py  (b) the plans: N = 1 forms, the step with the collective in it, the peer-to-peer exchange layer     decide / build_* / setup_exchange
     #   safety.py     (c) states_consistent / validate / the fall-back ladder - the N > 1 safety net                     (applied by runner.py)
     #   report.py     (d) the JSON line: value, schedules, xgmi, roofline (+ committed profiles), cpu_baseline + the oracle spot check
-    # then tools/bench_secondary.py: protocol 2 beside attention, the plugin path, every BASELINE config, the presets
+    # then (--full) tools/bench_secondary.py: protocol 2 beside attention, the plugin path, every BASELINE config, the presets
     args = parse()
     if args.print_config_key:
         print(json.dumps(config_key(args, args.gpus)))
@@ -109,27 +113,30 @@ def main():
         torch.cuda.synchronize(S.dev)
         del src, dst
     runner.timed_region(S)                        # warm-up ; validate ; K timed steps ; validate - falling back in-process (c)
-    # Everything below this line is commentary on a measurement that has been taken AND validated.  With more than one rank process it
-    # must not cost the line: the long run, the uncompressed exchange (ring hops no RCCL has seen from this code) and the other pattern run
-    # here for the first time on real links, and an error in them - the same on every rank - is reported in the line
+    if args.dump_outputs:
+        report.dump_outputs(S, args.dump_outputs)   # what the last timed step left, before any other leg advances the states
+    # Everything below this line is commentary on a measurement that has been taken AND validated (--full only).  With more than one rank
+    # process it must not cost the line: the long run, the uncompressed exchange (ring hops no RCCL has seen from this code) and the other
+    # pattern run here for the first time on real links, and an error in them - the same on every rank - is reported in the line
     # (`secondary_legs_error`) instead of ending the run.  One process: as loud as ever.
     S.long_ms = S.other_ms = S.two_ms = S.loop_ms = S.relay_ms = S.part_ms = S.coll_ms = None
     S.raw_legs, S.other_pattern_ms, S.raw_ms, S.secondary_error = {}, None, None, None
-    try:
-        runner.secondary_legs(S)
-        torch.cuda.synchronize(S.dev)
-        ge = S.lib.cfx_gate_errors(S.ctx)
-        if ge != 0:
-            raise RuntimeError(f"cfx_gate_errors = {ge}: a gated launch gave up waiting for its packets")
-        ok, why = runner.consistent(S)            # state sanity (bit-exact error-feedback consistency)
-        if not ok:
-            raise RuntimeError(why)
-        runner.raw_exchange_legs(S)
-    except Exception as e:  # noqa: BLE001
-        if S.world == 1:
-            raise SystemExit(f"[bench] {type(e).__name__}: {e}")
-        S.secondary_error = f"{type(e).__name__}: {e}"
-        print(f"[bench] rank {S.rank}: a leg after the timed region failed ({S.secondary_error}); the line carries the timed region", file=sys.stderr)
+    if args.full:
+        try:
+            runner.secondary_legs(S)
+            torch.cuda.synchronize(S.dev)
+            ge = S.lib.cfx_gate_errors(S.ctx)
+            if ge != 0:
+                raise RuntimeError(f"cfx_gate_errors = {ge}: a gated launch gave up waiting for its packets")
+            ok, why = runner.consistent(S)            # state sanity (bit-exact error-feedback consistency)
+            if not ok:
+                raise RuntimeError(why)
+            runner.raw_exchange_legs(S)
+        except Exception as e:  # noqa: BLE001
+            if S.world == 1:
+                raise SystemExit(f"[bench] {type(e).__name__}: {e}")
+            S.secondary_error = f"{type(e).__name__}: {e}"
+            print(f"[bench] rank {S.rank}: a leg after the timed region failed ({S.secondary_error}); the line carries the timed region", file=sys.stderr)
     out = report.build_line(S)                    # (d)
     if S.secondary_error is not None:
         out["secondary_legs_error"] = S.secondary_error
@@ -150,7 +157,7 @@ def main():
         report.teardown(S)
         return
     report.teardown(S)
-    if S.rank == 0 and S.world == 1 and not args.emulate_live and not args.no_secondary:
+    if args.full and S.rank == 0 and S.world == 1 and not args.emulate_live and not args.no_secondary:
         # the secondary legs that need nothing of this process's state (tools/bench_secondary.py): protocol 2 beside real attention and the
         # plugin path (child processes), every BASELINE configuration through the native replay AND through the plugin API, the presets
         del S.xs, S.own_base, S.peer_base

@@ -25,12 +25,38 @@ def _fake():
 
 
 def _bench(*args):
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--layers", "6", "--steps", "3", "--warmup", "1", "--long-steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--layers", "6", "--steps", "3", "--warmup", "1", "--long-steps", "3",
                         "--cpu-seconds", "0.5", "--overlap-steps", "0", *args], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1, "stdout carries ONE line, the JSON (library chatter - RCCL's version banner - belongs on stderr): %r" % lines[:-1]
     return json.loads(lines[-1])
+
+
+def test_plain_run_times_the_steps_and_dumps_what_the_last_step_left(tmp_path):
+    """Without --full the line carries the headline alone (no CPU baseline, no secondary leg), and --dump-outputs writes the states the last
+    timed step left as float32 within 64 MB: the same arguments twice give the same files, bit for bit."""
+    import numpy as np
+
+    def plain(out):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--layers", "6", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1, lines[:-1]
+        return json.loads(lines[-1])
+    d = plain(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["exchange_issued_by"] == "p2p" and d["launches_per_layer"] == 1
+    assert "cpu_baseline" not in d and d["long_run"] is None and d["two_launches_per_layer"] is None and "plugin_path" not in d
+    plain(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["own_state.npy", "peer_reconstructions.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all() and np.array_equal(a, b), n
 
 
 @pytest.mark.parametrize("warmup", [1, 4])
@@ -114,7 +140,7 @@ def test_bench_two_rank_processes_exchange_peer_to_peer():
     env = dict(os.environ)
     env.setdefault("GPU_MAX_HW_QUEUES", "8")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29613", os.path.join(REPO, "bench.py"), "--gpus", "2", "--same-gpu", "--backend", "gloo", "--layers", "6",
+                        "--master-port", "29613", os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--same-gpu", "--backend", "gloo", "--layers", "6",
                         "--steps", "4", "--warmup", "1", "--long-steps", "4", "--overlap-steps", "0", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=REPO, env=env)
     assert r.returncode == 0, r.stderr[-2500:]
@@ -136,7 +162,7 @@ def test_bench_poisoned_peer_state_falls_back_instead_of_dying(poison_step):
     env = dict(os.environ)
     env.setdefault("GPU_MAX_HW_QUEUES", "4")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(29620 + poison_step), os.path.join(REPO, "bench.py"), "--gpus", "2", "--same-gpu", "--backend", "gloo",
+                        "--master-port", str(29620 + poison_step), os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--same-gpu", "--backend", "gloo",
                         "--layers", "6", "--steps", "4", "--warmup", "2", "--long-steps", "4", "--overlap-steps", "0", "--no-cpu-baseline",
                         "--poison-after-step", str(poison_step)],
                        capture_output=True, text=True, timeout=600, cwd=REPO, env=env)

@@ -222,9 +222,11 @@ def test_function_level_mirrors(cpu_kernels):
         S.slowpath_compress(d, T.IDENTITY)
 
 
-def test_profiler_scopes_cpu():
+def test_profiler_scopes_cpu(monkeypatch):
     import time
+    import torch
     from compactfusion_amd.prof import Profiler, prof_summary
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # a host without a GPU, also where the suite runs beside one
     p = Profiler()
     Profiler._singleton = p
     with Profiler.scope("total", cpu=True):

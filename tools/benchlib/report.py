@@ -290,6 +290,31 @@ def add_cpu_baseline(S, out) -> None:
                                                        f"{S.steps_run} steps of this run == C oracle replay, bit for bit")
 
 
+DUMP_SAMPLE = {"own_state": (0, 4 << 20), "peer_reconstructions": (1, 8 << 20)}      # name: (seed, elements) - 48 MiB of float32 in all
+
+
+def dump_outputs(S, out_dir) -> None:
+    """--dump-outputs: what the last timed step left for a caller of the path, as float32 .npy files (the states are fp16: exact).
+
+    own_state             own_base [L, 2, N, C]: the rank's error-feedback states of its K,V (what every peer reconstructs)
+    peer_reconstructions  peer_base [L, 7, 2, N, C]: the 7 logical peers' K,V as this rank reconstructed them
+    A tensor larger than its budget is sampled: sorted flat indices drawn by np.random.default_rng(seed), the same for every run with the
+    same arguments, so two builds can be compared element for element.  Rank 0 only."""
+    if S.rank != 0:
+        return
+    import numpy as np
+    S.torch.cuda.synchronize(S.dev)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("own_state", S.own_base), ("peer_reconstructions", S.peer_base)):
+        seed, budget = DUMP_SAMPLE[name]
+        if t.numel() <= budget:
+            host = t.float().cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), size=budget, dtype=np.int64))
+            host = t.reshape(-1).index_select(0, S.torch.from_numpy(idx).to(S.dev)).float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), host)
+
+
 def teardown(S) -> None:
     """Communicators, plans, streams, IPC mappings - torn down before the line is written (RCCL prints through its own stdio buffer)."""
     # tear the communicators down first and flush C stdio (RCCL prints a version banner through its own stdio buffer),

@@ -112,7 +112,7 @@ def build_local_plans(S) -> None:
             built.append(plan)
         return built
     S.plans_inorder = _build("inorder")
-    S.plans_pipe = None if S.int2 else _build("pipelined")
+    S.plans_pipe = None if (S.int2 or (not S.pipelined and S.args.no_secondary)) else _build("pipelined")
     S.plans_gated = _build("gated") if (S.gated or (S.real_live == 1 and not S.args.emulate_live and not S.pipelined and not S.args.no_secondary)) else None
     S.plans = S.plans_pipe if S.pipelined else (S.plans_gated if S.gated else S.plans_inorder)
 

@@ -101,7 +101,20 @@ def parse():
                     help="print the configuration key profile summaries are matched against (tools/collect_profiles.sh) and exit")
     ap.add_argument("--event-stride", type=int, default=29,
                     help="bracket every k-th launch of the profiled kernels with hipEvents (an event pair costs a few us of stream time)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-kernel events and the roofline, the copy-rate probe, the "
+                         "long run and the other schedules, the uncompressed exchange, the CPU baseline with the oracle parity spot check, the "
+                         "plugin path, every BASELINE configuration, the presets.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step left for its caller - the rank's own error-feedback states and "
+                         "the peers' reconstructed K,V, a fixed seeded sample as float32 - to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run does what the headline needs and nothing else: every leg, probe and check beside it belongs to --full
+        args.no_kernel_events = args.no_copy_rate = args.no_secondary = args.no_raw_baseline = True
+        args.no_cpu_baseline = args.no_config_table = True
+        args.overlap_steps = args.plugin_steps = 0
+    return args
 
 
 def cpu_baseline(seconds: float, codec: str = "binary"):

@@ -15,9 +15,9 @@ export GPU_MAX_HW_QUEUES=8
 #    exchange kernel per layer on the exchange stream, no collective).  --overlap-steps 0 and --no-secondary keep the other legs' kernels out of the averages.
 #    Every profiled command runs under `timeout`: a profiler that serialises dispatches would leave the flag-ordered launch waiting for a kernel
 #    that cannot start.
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python3 "$R/bench.py" --steps 20 --warmup 3 --no-secondary --overlap-steps 0 --plugin-steps 0 --no-config-table > "$OUT/bench_under_rocprof.log" 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python3 "$R/bench.py" --full --steps 20 --warmup 3 --no-secondary --overlap-steps 0 --plugin-steps 0 --no-config-table > "$OUT/bench_under_rocprof.log" 2>&1 < /dev/null
 # 1b. the same trace of the two-launch schedule (what runs with more than one rank execute)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace2" -o bench -- python3 "$R/bench.py" --own-ef ride --steps 20 --warmup 3 --no-secondary --overlap-steps 0 --plugin-steps 0 --no-config-table > "$OUT/bench2_under_rocprof.log" 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace2" -o bench -- python3 "$R/bench.py" --full --own-ef ride --steps 20 --warmup 3 --no-secondary --overlap-steps 0 --plugin-steps 0 --no-config-table > "$OUT/bench2_under_rocprof.log" 2>&1 < /dev/null
 ST2=$(find "$OUT/trace2" -name "*kernel_stats.csv" 2>/dev/null | head -1)
 [ -n "$ST2" ] && cp "$ST2" "$OUT/r06_bench_two_launch_kernel_stats.csv"
 rm -rf "$OUT/trace2"
@@ -26,14 +26,14 @@ rm -rf "$OUT/trace2"
 #    (k_absmean_compress<bits,gated> with its in-launch gate: identical loads and stores, one stream) and the file says so.
 PSTEPS=3
 PNOTE="counter passes serialise dispatches: taken on --no-collective --own-ef gated, the same kernel (k_absmean_compress<true, 4, true>) with its in-launch gate instead of the exchange stream's flag - identical loads and stores"
-timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o pmc -- python3 "$R/bench.py" --no-collective --own-ef gated --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_fetch.log" 2>&1 < /dev/null
-timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o pmc -- python3 "$R/bench.py" --no-collective --own-ef gated --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_write.log" 2>&1 < /dev/null
+timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o pmc -- python3 "$R/bench.py" --full --no-collective --own-ef gated --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_fetch.log" 2>&1 < /dev/null
+timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o pmc -- python3 "$R/bench.py" --full --no-collective --own-ef gated --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_write.log" 2>&1 < /dev/null
 cd "$R"
 python3 tools/pmc_summary.py "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/r06_pmc_traffic.json" "$KEY" $PSTEPS "$PNOTE" > /dev/null
 # 2b. the same counters for the two-launch schedule
 cd /tmp
-timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch2" -o pmc -- python3 "$R/bench.py" --own-ef ride --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_fetch2.log" 2>&1 < /dev/null
-timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write2" -o pmc -- python3 "$R/bench.py" --own-ef ride --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_write2.log" 2>&1 < /dev/null
+timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch2" -o pmc -- python3 "$R/bench.py" --full --own-ef ride --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_fetch2.log" 2>&1 < /dev/null
+timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write2" -o pmc -- python3 "$R/bench.py" --full --own-ef ride --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary --overlap-steps 0 --copy-probe 8 > "$OUT/pmc_write2.log" 2>&1 < /dev/null
 cd "$R"
 KEY2=$(python3 "$R/bench.py" --own-ef ride --print-config-key)
 python3 tools/pmc_summary.py "$OUT/pmc_fetch2" "$OUT/pmc_write2" "$OUT/r06_pmc_traffic_two_launch.json" "$KEY2" $PSTEPS > /dev/null
@@ -47,17 +47,17 @@ rm -rf "$OUT/trace" "$OUT/pmc_fetch" "$OUT/pmc_write"
 cp "$OUT/r06_pmc_traffic.json" profiles/r06_pmc_traffic.json
 cp "$OUT/r06_bench_kernel_durations.json" profiles/r06_bench_kernel_durations.json
 # 3. the bench lines themselves: headline, 2-bit preset, loop-back one-launch form, N > 1 plumbing over the loop-back library
-python3 bench.py > "$OUT/r06_bench_n1.json" 2>/dev/null
-python3 bench.py --codec int2 --overlap-steps 0 --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_int2.json" 2>/dev/null
-python3 bench.py --no-collective --own-ef gated --overlap-steps 0 --no-cpu-baseline --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_loopback_one_launch.json" 2>/dev/null
-python3 bench.py --own-ef ride --overlap-steps 0 --no-cpu-baseline --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_two_launch.json" 2>/dev/null
-python3 bench.py --p2p off --overlap-steps 0 --no-cpu-baseline --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_collective_in_path.json" 2>/dev/null
-python3 bench.py --emulate-live 8 --rccl-lib "$FAKE" --no-cpu-baseline --long-steps 20 > "$OUT/r06_bench_emulated_live8.json" 2>/dev/null
-CFX_FAKE_RCCL_FAT=1 python3 bench.py --emulate-live 8 --rccl-lib "$FAKE" --no-cpu-baseline --long-steps 20 > "$OUT/r06_bench_emulated_live8_fat.json" 2>/dev/null
-timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29617 bench.py --gpus 2 --same-gpu --backend gloo --no-cpu-baseline --overlap-steps 0 --steps 20 --warmup 3 --long-steps 20 2>/dev/null | tail -1 > "$OUT/r06_bench_p2p_two_processes_one_gpu.json"
+python3 bench.py --full > "$OUT/r06_bench_n1.json" 2>/dev/null
+python3 bench.py --full --codec int2 --overlap-steps 0 --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_int2.json" 2>/dev/null
+python3 bench.py --full --no-collective --own-ef gated --overlap-steps 0 --no-cpu-baseline --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_loopback_one_launch.json" 2>/dev/null
+python3 bench.py --full --own-ef ride --overlap-steps 0 --no-cpu-baseline --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_two_launch.json" 2>/dev/null
+python3 bench.py --full --p2p off --overlap-steps 0 --no-cpu-baseline --plugin-steps 0 --no-config-table > "$OUT/r06_bench_n1_collective_in_path.json" 2>/dev/null
+python3 bench.py --full --emulate-live 8 --rccl-lib "$FAKE" --no-cpu-baseline --long-steps 20 > "$OUT/r06_bench_emulated_live8.json" 2>/dev/null
+CFX_FAKE_RCCL_FAT=1 python3 bench.py --full --emulate-live 8 --rccl-lib "$FAKE" --no-cpu-baseline --long-steps 20 > "$OUT/r06_bench_emulated_live8_fat.json" 2>/dev/null
+timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29617 bench.py --full --gpus 2 --same-gpu --backend gloo --no-cpu-baseline --overlap-steps 0 --steps 20 --warmup 3 --long-steps 20 2>/dev/null | tail -1 > "$OUT/r06_bench_p2p_two_processes_one_gpu.json"
 python3 tools/xlayer_room_loop.py 2>&1 | grep -v amdgpu.ids > "$OUT/r06_xlayer_room_loop.txt"
 SHARE=0 python3 tools/xlayer_room_loop.py 2>&1 | grep -v amdgpu.ids > "$OUT/r06_xlayer_room_loop_stream_churn.txt"
-python3 bench.py --emulate-live 8 --rccl-lib "$FAKE" --exchange-pattern relay --no-cpu-baseline --long-steps 20 > "$OUT/r06_bench_emulated_live8_relay.json" 2>/dev/null
+python3 bench.py --full --emulate-live 8 --rccl-lib "$FAKE" --exchange-pattern relay --no-cpu-baseline --long-steps 20 > "$OUT/r06_bench_emulated_live8_relay.json" 2>/dev/null
 # 4. the deployable path with real attention (SURVEY 8d protocol 2): all legs, then kernel traces of the lane leg and of attention alone
 python3 tools/overlap_bench.py --steps 20 --json "$OUT/r06_overlap.json" > /dev/null 2>&1
 bash tools/lane_trace.sh "$OUT/lane" > /dev/null 2>&1
@@ -82,14 +82,14 @@ python3 tools/lrs_stamps.py 2>&1 | grep -v amdgpu.ids > "$OUT/r06_lowrank_slab_t
 #    PMC traffic of the other codecs' launches at their BASELINE shapes
 python3 tools/plugin_path_bench.py --json "$OUT/r06_plugin_path.json" --quiet > /dev/null 2>&1
 python3 tools/gated_stamps.py 2>&1 | grep -v amdgpu.ids > "$OUT/r06_gated_layer_timeline.txt"
-timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29618 bench.py --gpus 2 --same-gpu --backend gloo --no-cpu-baseline --overlap-steps 0 --steps 20 --warmup 3 --long-steps 20 --poison-after-step 5 2>"$OUT/r06_bench_poisoned_p2p.stderr.txt" | tail -1 > "$OUT/r06_bench_poisoned_p2p_two_processes_one_gpu.json"
+timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29618 bench.py --full --gpus 2 --same-gpu --backend gloo --no-cpu-baseline --overlap-steps 0 --steps 20 --warmup 3 --long-steps 20 --poison-after-step 5 2>"$OUT/r06_bench_poisoned_p2p.stderr.txt" | tail -1 > "$OUT/r06_bench_poisoned_p2p_two_processes_one_gpu.json"
 cd /tmp
 TR2=$OUT/trace_xl
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$TR2" -- python3 "$R/bench.py" --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-kernel-events --overlap-steps 0 --plugin-steps 0 --no-config-table > /dev/null 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$TR2" -- python3 "$R/bench.py" --full --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-kernel-events --overlap-steps 0 --plugin-steps 0 --no-config-table > /dev/null 2>&1 < /dev/null
 python3 "$R/tools/xlayer_trace.py" "$(find "$TR2" -name '*kernel_trace.csv' | head -1)" > "$OUT/r06_layer_kernel_trace.txt" 2>&1
 rm -rf "$TR2"
 # (the same step with the exchange as a kernel on the exchange stream - the form until mid round 4, still what `--p2p off` runs)
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$TR2" -- python3 "$R/bench.py" --p2p off --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-kernel-events --overlap-steps 0 --plugin-steps 0 --no-config-table > /dev/null 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$TR2" -- python3 "$R/bench.py" --full --p2p off --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-kernel-events --overlap-steps 0 --plugin-steps 0 --no-config-table > /dev/null 2>&1 < /dev/null
 python3 "$R/tools/xlayer_trace.py" "$(find "$TR2" -name '*kernel_trace.csv' | head -1)" > "$OUT/r06_layer_vs_flag_kernel_trace.txt" 2>&1
 rm -rf "$TR2"
 cd "$R"
