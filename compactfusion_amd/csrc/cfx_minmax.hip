@@ -12,9 +12,16 @@
 #include "cfx_device.h"
 #include "cfx_host.h"
 
+// Running min / max that PROPAGATE NaN, as torch.min / torch.max do (compress_quantize.py:452-453, :552-553): a NaN operand replaces
+// the running value, and a NaN running value is only ever replaced by another NaN.  Every stage uses them - the element loop, the
+// merge of the waves' values and the merge of the published partials - so one NaN delta makes its channel's min and max NaN.
+// (+-0 keep the first seen, as a plain compare-and-select does.)
+__device__ __forceinline__ h16 hmin_nan(h16 a, h16 m) { return (a < m || a != a) ? a : m; }
+__device__ __forceinline__ h16 hmax_nan(h16 a, h16 m) { return (a > m || a != a) ? a : m; }
+
 // ---------------------------------------------------------------------------------------------------
 // per-channel min/max statistics pass (int4 / int8)    compress_quantize.py:452-453, :552-553
-//   part[p][c] = {min, max} of (x-base) over the tile's rows (fp16 compares are exact)
+//   part[p][c] = {min, max} of (x-base) over the tile's rows (fp16 compares are exact; NaN propagates)
 // ---------------------------------------------------------------------------------------------------
 template <bool WT>
 __device__ __forceinline__ void minmax_stats_body(const cfx_comp_item& it, int N, int C, int R, int bx, int by, unsigned* part) {
@@ -42,8 +49,8 @@ __device__ __forceinline__ void minmax_stats_body(const cfx_comp_item& it, int N
                 const h16x8 d = xv[j] - bv[j];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
-                    mn[i] = d[i] < mn[i] ? d[i] : mn[i];
-                    mx[i] = d[i] > mx[i] ? d[i] : mx[i];
+                    mn[i] = hmin_nan(d[i], mn[i]);
+                    mx[i] = hmax_nan(d[i], mx[i]);
                 }
             }
         }
@@ -61,8 +68,8 @@ __device__ __forceinline__ void minmax_stats_body(const cfx_comp_item& it, int N
 #pragma unroll
             for (int w = 1; w < WAVES; ++w) {
                 const h16 a2 = hfrom((u16)(sm[w][s] & 0xffff)), b2 = hfrom((u16)(sm[w][s] >> 16));
-                a = a2 < a ? a2 : a;
-                b = b2 > b ? b2 : b;
+                a = hmin_nan(a2, a);
+                b = hmax_nan(b2, b);
             }
             const unsigned v = (unsigned)hbits(a) | ((unsigned)hbits(b) << 16);
             if (WT) st_wt(&part[(size_t)by * C + cc], v); else part[(size_t)by * C + cc] = v;
@@ -130,8 +137,8 @@ __global__ __launch_bounds__(1024) void k_minmax_finalize(BatchC batch, int N, i
         for (int p = q; p < P; p += 4) {
             const unsigned v = part[(size_t)p * C + c];
             const h16 a = hfrom((u16)(v & 0xffff)), b = hfrom((u16)(v >> 16));
-            mn = a < mn ? a : mn;
-            mx = b > mx ? b : mx;
+            mn = hmin_nan(a, mn);
+            mx = hmax_nan(b, mx);
         }
     }
     red[q][cl] = (unsigned)hbits(mn) | ((unsigned)hbits(mx) << 16);
@@ -140,8 +147,8 @@ __global__ __launch_bounds__(1024) void k_minmax_finalize(BatchC batch, int N, i
 #pragma unroll
     for (int k = 1; k < 4; ++k) {
         const h16 a = hfrom((u16)(red[k][cl] & 0xffff)), b = hfrom((u16)(red[k][cl] >> 16));
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
+        mn = hmin_nan(a, mn);
+        mx = hmax_nan(b, mx);
     }
     minmax_write_scales(it, N, C, codec, c, mn, mx);
 }
@@ -180,8 +187,8 @@ __global__ __launch_bounds__(NTHR) void k_minmax_compress(BatchC batch, int N, i
         for (int j = 0; j < FUSED_CH; ++j) {
             const h16 a0 = hfrom((u16)(v0[j] & 0xffff)), b0 = hfrom((u16)(v0[j] >> 16));
             const h16 a1 = hfrom((u16)(v1[j] & 0xffff)), b1 = hfrom((u16)(v1[j] >> 16));
-            mn0 = a0 < mn0 ? a0 : mn0; mx0 = b0 > mx0 ? b0 : mx0;
-            mn1 = a1 < mn1 ? a1 : mn1; mx1 = b1 > mx1 ? b1 : mx1;
+            mn0 = hmin_nan(a0, mn0); mx0 = hmax_nan(b0, mx0);
+            mn1 = hmin_nan(a1, mn1); mx1 = hmax_nan(b1, mx1);
         }
     }
     if (c0 < C) minmax_write_scales(it, N, C, codec, c0, mn0, mx0);
@@ -350,8 +357,8 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
         if (rv[q]) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                mn[i] = d[i] < mn[i] ? d[i] : mn[i];
-                mx[i] = d[i] > mx[i] ? d[i] : mx[i];
+                mn[i] = hmin_nan(d[i], mn[i]);
+                mx[i] = hmax_nan(d[i], mx[i]);
             }
         }
     }
@@ -371,8 +378,8 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
         for (int w = 1; w < NW; ++w) {
             const unsigned v = sm32[w * TILE_C + sidx];
             const h16 a2 = hfrom((u16)(v & 0xffff)), b2 = hfrom((u16)(v >> 16));
-            lo = a2 < lo ? a2 : lo;
-            hi = b2 > hi ? b2 : hi;
+            lo = hmin_nan(a2, lo);
+            hi = hmax_nan(b2, hi);
         }
         // the partial AND its "published" mark in one 8-byte store: nobody waits for a store to be acknowledged before a flag can follow
         if (ch < C) st_wt(&part[(size_t)by * C + ch], tag | (unsigned)hbits(lo) | ((unsigned)hbits(hi) << 16));
@@ -420,8 +427,8 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const h16 a0 = hfrom((u16)(v[j] & 0xffff)), b0 = hfrom((u16)((unsigned)v[j] >> 16));
-                lo = a0 < lo ? a0 : lo;
-                hi = b0 > hi ? b0 : hi;
+                lo = hmin_nan(a0, lo);
+                hi = hmax_nan(b0, hi);
             }
         }
         minmax_scale_of<INT4>(lo, hi, scale, second);
@@ -449,8 +456,8 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const h16 a0 = hfrom((u16)(v[j] & 0xffff)), b0 = hfrom((u16)((unsigned)v[j] >> 16));
-                    lo = a0 < lo ? a0 : lo;
-                    hi = b0 > hi ? b0 : hi;
+                    lo = hmin_nan(a0, lo);
+                    hi = hmax_nan(b0, hi);
                 }
             }
             failed = __syncthreads_or(failed ? 1 : 0) != 0;     // (sm32: the publish above has read it) - a wave that gave up: no scales from this tile
@@ -461,8 +468,8 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
                 for (int w = 1; w < NW; ++w) {
                     const unsigned u = sm32[w * 64 + t.lane];
                     const h16 a0 = hfrom((u16)(u & 0xffff)), b0 = hfrom((u16)(u >> 16));
-                    lo = a0 < lo ? a0 : lo;
-                    hi = b0 > hi ? b0 : hi;
+                    lo = hmin_nan(a0, lo);
+                    hi = hmax_nan(b0, hi);
                 }
                 h16 sc1;
                 u16 sec1;

@@ -19,6 +19,9 @@
 // The 8 elements at flat offset e of one tensor (whole waves call it together: the 16-wide blocks talk to their neighbour lanes).
 // WT: the packet goes out write-through - workgroups of the same launch read it (k_topk_layer).
 #define TOPK_PUT(ptr, v) do { if (WT) st_wt(ptr, v); else *(ptr) = (v); } while (0)
+// Magnitude v beats the best so far b in tl.argmax's order (compress_topk.py:82-83): larger, or a NaN against a number - NaN is above
+// everything, +inf included, and a later NaN does not replace an earlier one (the first maximum / the first NaN wins).
+__device__ __forceinline__ bool topk_beats(h16 v, h16 b) { return v > b || (v != v && b == b); }
 template <int M, bool WT>
 __device__ __forceinline__ void topk_compress_unit(const cfx_comp_item& it, size_t e, size_t E, int flags, h16x8 xv, h16x8 bv) {
     const h16* x = (const h16*)it.x;
@@ -41,7 +44,7 @@ __device__ __forceinline__ void topk_compress_unit(const cfx_comp_item& it, size
 #pragma unroll
             for (int i = 1; i < M; ++i) {
                 const h16 v = a[hb * M + i];
-                if (v > bestv) { bestv = v; best = i; }     // strict: first maximum wins (tl.argmax)
+                if (topk_beats(v, bestv)) { bestv = v; best = i; }     // strict: first maximum wins (tl.argmax)
             }
             sel[hb] = best;
             keep |= 1u << (hb * M + best);
@@ -58,13 +61,13 @@ __device__ __forceinline__ void topk_compress_unit(const cfx_comp_item& it, size
         int best = 0;
         h16 bestv = a[0];
 #pragma unroll
-        for (int i = 1; i < 8; ++i) if (a[i] > bestv) { bestv = a[i]; best = i; }
+        for (int i = 1; i < 8; ++i) if (topk_beats(a[i], bestv)) { bestv = a[i]; best = i; }
         const int odd = threadIdx.x & 1;
         const unsigned pb = hbits(bestv);
         const unsigned ob = __shfl_xor(pb, 1, 64);
         const int oi = __shfl_xor(best, 1, 64);
         // lower lane wins ties (its elements come first)
-        const bool mine = odd ? (hfrom((u16)pb) > hfrom((u16)ob)) : !(hfrom((u16)ob) > hfrom((u16)pb));
+        const bool mine = odd ? topk_beats(hfrom((u16)pb), hfrom((u16)ob)) : !topk_beats(hfrom((u16)ob), hfrom((u16)pb));
         const int selidx = mine ? (best + 8 * odd) : (oi + 8 * (1 - odd));   // index within the 16-wide half-block
         if (mine) { keep |= 1u << best; TOPK_PUT(&val[e / 16], hbits(d[best])); }
         const int other = __shfl_xor(selidx, 2, 64);

@@ -32,6 +32,15 @@
  *   INT4    [ codes N*C/2 B : byte [n/2][c] = q[n][c] | q[n+1][c]<<4           | scale C fp16 | min C fp16 ]   compress_quantize.py:566-573
  *   INT8    [ q     N*C   B : int8                                             | scale C fp16 | zp  C int16 ]  compress_quantize.py:463-471
  *   TOPK    [ val N*C/m fp16 | idx N*C/(2m) B : (i1<<4)|i2 per 2m-block of the flat (-1,1024) view ]           slowpath.py:76-79
+ *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
+ *   and N odd, int4 with C % 16 == 8 and N/2 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
+ *
+ * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
+ *   INT4 / INT8: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
+ *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
+ *   TOPK:        |delta| is ranked as the reference's tl.argmax ranks it: NaN above everything, +inf included; the first NaN wins.
+ *   BINARY / INT2: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
+ *                NaN; the outputs are finite garbage or NaN, and need not match the reference.
  */
 #ifndef CFX_H
 #define CFX_H
@@ -52,7 +61,7 @@ enum cfx_status {
     CFX_OK = 0,
     CFX_ERR_NULL = -1,       /* a required pointer is NULL */
     CFX_ERR_SHAPE = -2,      /* N/C/param violate the codec's divisibility rules */
-    CFX_ERR_ALIGN = -3,      /* a tensor pointer is not 16-byte aligned / packet not 2-byte aligned */
+    CFX_ERR_ALIGN = -3,      /* a tensor or packet pointer is not 16-byte aligned */
     CFX_ERR_CODEC = -4,      /* unknown codec id */
     CFX_ERR_BATCH = -5,      /* batch < 1 or > CFX_MAX_BATCH */
     CFX_ERR_LAUNCH = -6,     /* hipGetLastError() after a launch was not hipSuccess */
@@ -81,7 +90,7 @@ typedef struct cfx_comp_item {
     const void* x;        /* (N,C) fp16, 16-byte aligned */
     const void* base;     /* (N,C) fp16, 16-byte aligned, or NULL */
     void*       new_base; /* (N,C) fp16, 16-byte aligned, or NULL */
-    void*       packet;   /* cfx_packet_bytes() bytes, 2-byte aligned (16-byte aligned is faster) */
+    void*       packet;   /* cfx_packet_bytes() bytes, 16-byte aligned */
 } cfx_comp_item;
 
 /* One tensor of a decompress batch.  recon = base + decode(packet) (base NULL: recon = decode(packet)).

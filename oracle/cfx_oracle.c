@@ -220,10 +220,17 @@ int oracle_compress(int codec, const h16* x, const h16* base, h16* new_base, uin
 #pragma omp for schedule(static)
             for (int n = 0; n < N; ++n) {
                 delta_row(x + (size_t)n * C, base ? base + (size_t)n * C : NULL, d, C);
-                for (int c = 0; c < C; ++c) { const float v = h2f(d[c]); if (v < lmn[c]) lmn[c] = v; if (v > lmx[c]) lmx[c] = v; }
+                for (int c = 0; c < C; ++c) {   /* NaN propagates (torch.min / torch.max): a NaN, once in, is never replaced */
+                    const float v = h2f(d[c]);
+                    if (v < lmn[c] || v != v) lmn[c] = v;
+                    if (v > lmx[c] || v != v) lmx[c] = v;
+                }
             }
 #pragma omp critical
-            for (int c = 0; c < C; ++c) { if (lmn[c] < mn[c]) mn[c] = lmn[c]; if (lmx[c] > mx[c]) mx[c] = lmx[c]; }
+            for (int c = 0; c < C; ++c) {
+                if ((lmn[c] < mn[c] || lmn[c] != lmn[c]) && mn[c] == mn[c]) mn[c] = lmn[c];
+                if ((lmx[c] > mx[c] || lmx[c] != lmx[c]) && mx[c] == mx[c]) mx[c] = lmx[c];
+            }
             free(lmn); free(lmx); free(d);
         }
         for (int c = 0; c < C; ++c) {
@@ -261,14 +268,14 @@ int oracle_compress(int codec, const h16* x, const h16* base, h16* new_base, uin
                             float vf = hnan(v) ? 0.f : h2f(v);
                             if (vf < -128.f) vf = -128.f; if (vf > 127.f) vf = 127.f;
                             ((int8_t*)pk)[(size_t)n * C + c] = (int8_t)vf;
-                            rv[c] = hmul(hsub(f2h(vf), zp), S[c]);
+                            rv[c] = hmul(hsub(f2h((float)(int)vf), zp), S[c]);     /* the code as an integer: rint of a small negative is -0 */
                         } else {
                             h16 v = hrint(hdivh(hsub(d[c], M[c]), S[c]));
                             float vf = hnan(v) ? 0.f : h2f(v);
                             if (vf < 0.f) vf = 0.f; if (vf > 15.f) vf = 15.f;
                             uint8_t* q = pk + (size_t)k * C + c;
                             if (h == 0) *q = (uint8_t)vf; else *q |= (uint8_t)((unsigned)vf << 4);
-                            rv[c] = hadd(hmul(f2h(vf), S[c]), M[c]);
+                            rv[c] = hadd(hmul(f2h((float)(int)vf), S[c]), M[c]);
                         }
                     }
                     store_state(new_base ? new_base + (size_t)n * C : NULL, xr, br, rv, C, flags);
@@ -293,7 +300,8 @@ int oracle_compress(int codec, const h16* x, const h16* base, h16* new_base, uin
             for (int h = 0; h < 2; ++h) {
                 int best = 0;
                 float bv = h2f((h16)(d[h * m] & 0x7fffu));
-                for (int i = 1; i < m; ++i) { const float v = h2f((h16)(d[h * m + i] & 0x7fffu)); if (v > bv) { bv = v; best = i; } }
+                /* NaN beats everything, +inf included; the first NaN wins (tl.argmax) */
+                for (int i = 1; i < m; ++i) { const float v = h2f((h16)(d[h * m + i] & 0x7fffu)); if (v > bv || (v != v && bv == bv)) { bv = v; best = i; } }
                 sel[h] = (unsigned)best;
                 val[b * 2 + h] = d[h * m + best];
                 rv[h * m + best] = d[h * m + best];

@@ -37,6 +37,11 @@ Numerics contract
   compiled-mode golden vectors are checked only to the reference's own test tolerances.
 * float -> integer conversion of NaN is defined as 0 (what the GPU conversion
   instructions return; the reference relies on undefined behaviour there).
+* Non-finite input: int8 / int4 propagate NaN through the per-channel min / max (numpy's
+  min / max, like the reference's torch.min / torch.max), top-k ranks NaN above +inf with
+  the first NaN winning (tl.argmax) - pinned by golden G16.  1-bit and 2-bit outputs on
+  non-finite input are UNSPECIFIED (the exact integer sums cannot carry inf / NaN; the HIP
+  kernels and this oracle need not agree there).
 """
 from __future__ import annotations
 
@@ -416,10 +421,12 @@ def sim_int2_minmax(x):
 # --------------------------------------------------------------------------------------
 def _first_argmax_abs(blocks16):
     """argmax |x| along the last axis, first maximum wins (tl.argmax, compress_topk.py:82-83);
-    NaN magnitudes are treated as larger than everything (max-propagating)."""
+    NaN is larger than everything, +inf included, and the first NaN wins (what tl.argmax and torch.argmax
+    return: golden G16)."""
     a = np.abs(blocks16).astype(np.float32)
-    a = np.where(np.isnan(a), np.float32(np.inf), a)
-    return np.argmax(a, axis=-1)
+    nan = np.isnan(a)
+    am = np.argmax(np.where(nan, np.float32(0), a), axis=-1)
+    return np.where(nan.any(axis=-1), np.argmax(nan, axis=-1), am)
 
 
 def topk_compress(x2d, m):

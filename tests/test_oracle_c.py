@@ -3,6 +3,7 @@ numpy oracle bit for bit.  CPU only."""
 import numpy as np
 import pytest
 
+import _nonfinite as NF
 from oracle import c_oracle as CO
 from oracle import ref_np as R
 
@@ -95,3 +96,29 @@ def test_c_oracle_edge_cases(codec, param):
         pkt_c, nb_c = CO.compress(codec, xx, bb, N, C, param)
         assert _same(pkt_c, pkt_np)
         assert _same(nb_c, R.bits(nb_np))
+
+
+@pytest.mark.parametrize("case", NF.cases(), ids=NF.ids())
+def test_c_oracle_nonfinite_golden(case):
+    """G16: NaN propagates through the per-channel min / max and outranks +inf in the top-k pick (first NaN wins), as in the
+    reference (tests/golden/make_golden_nonfinite.py)"""
+    _, codec, param, x, base, want_pkt, want_rec = case
+    N, C = x.shape
+    pkt, nb = CO.compress(codec, x, base, N, C, param)
+    NF.same_bits(pkt, want_pkt, "packet")
+    NF.same_bits(nb, want_rec, "error-feedback state")
+    NF.same_bits(CO.decompress(codec, pkt, base, N, C, param), want_rec, "reconstruction")
+
+
+@pytest.mark.parametrize("codec", ["int8", "int4"])
+def test_c_oracle_state_without_base(codec):
+    """residual 0 (base NULL): the state is the decoded packet itself, so the sign of a zero code shows - a code from rint of a small
+    negative value is the integer 0 (+0 when decoded), as the numpy oracle and the kernels have it"""
+    N, C = 64, 512
+    x, _ = _inputs(11, N, C)
+    x[:, 3] = F16(-0.001); x[0, 3] = F16(-3.0); x[1, 3] = F16(3.0)         # codes near 0 from the negative side
+    x[:, 5] = F16(-0.0); x[2, 5] = F16(2.0)                                  # int4: min -0 + 0 * scale
+    pkt_np, rec_np = R.compress(codec, x, None, 0)
+    pkt_c, nb_c = CO.compress(codec, x, None, N, C, 0, update=True)
+    assert _same(pkt_c, pkt_np)
+    assert _same(nb_c, R.bits(rec_np)), "state without base"

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _golden as G
+import _nonfinite as NF
 from oracle import ref_np as R
 
 F16 = np.float16
@@ -238,3 +239,36 @@ def test_compiled_mode_captures_within_reference_tolerances(shape, seed):
         q2, c2, t2 = R.quantize_int2(delta)
         assert float((q2 != G.get(fn, f"{tag}/i2/q")).mean()) < 5e-3
         assert G.rel_err(R.bits(R.dequantize_int2(q2, c2, t2)), G.get(fn, f"{tag}/i2/deq")) < 0.02
+
+
+# ---- G16: non-finite residuals (NaN, +-inf, inf - inf).  The reference's torch.min / torch.max propagate NaN and its tl.argmax
+# ---- ranks NaN above +inf, the first NaN winning (tests/golden/make_golden_nonfinite.py); the oracle must do the same.
+@pytest.mark.parametrize("case", NF.cases(), ids=NF.ids())
+def test_g16_nonfinite(case):
+    _, codec, param, x, base, want_pkt, want_rec = case
+    N, C = x.shape
+    with np.errstate(invalid="ignore", over="ignore"):
+        pkt, nb = R.residual_compress(codec, x, base, param)
+        rec = R.residual_decompress(codec, pkt, base, N, C, param)
+    NF.same_bits(pkt, want_pkt, "packet")
+    NF.same_bits(R.bits(nb), want_rec, "error-feedback state")
+    NF.same_bits(R.bits(rec), want_rec, "reconstruction")
+
+
+def test_g16_fixture_holds_the_cases():
+    """the fixture exercises what it claims: NaN channels (scale NaN, codes 0) and half-blocks where NaN outranks +inf"""
+    cs = {c[0]: c for c in NF.cases()}
+    for k in ("mm-int8", "mm-int4"):
+        _, codec, _, x, base, pkt, rec = cs[k]
+        N, C = x.shape
+        q_bytes = N * C if codec == "int8" else N * C // 2
+        scale = pkt[q_bytes // 2:q_bytes // 2 + C]
+        nan_ch = ((scale & 0x7fff) > 0x7c00)
+        assert nan_ch[[3, 5, 6, 9, 40, 41, 127]].all() and nan_ch.sum() == 7, np.nonzero(nan_ch)
+        assert np.isinf(scale.view(F16)[[20, 21, 22, 23, 42]]).all()
+    _, _, m, x, base, pkt, _ = cs["tk-topk16"]
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = (x.view(F16) - base.view(F16)).astype(F16).reshape(-1, 2, 16)
+    a = np.abs(d.astype(np.float32))
+    both = np.isnan(a).any(-1) & np.isposinf(a).any(-1)
+    assert both.sum() >= 2                              # NaN and +inf in one half-block, in either order
