@@ -120,8 +120,6 @@ SYMBOLS = [
     ("cfx_plan_size", ctypes.c_int, [ctypes.c_void_p]),
     ("cfx_plan_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     ("cfx_plan_run_x", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p]),
-    ("cfx_plan_run_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p]),
-    ("cfx_plan_join", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     ("cfx_plan_run_pipelined", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     ("cfx_plan_finalize", ctypes.c_int, [ctypes.c_void_p]),
     ("cfx_residual2_delta", ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]),
@@ -190,7 +188,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         fn = getattr(lib, name)     # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args
-    if lib.cfx_abi_version() != 1:
+    if lib.cfx_abi_version() != 2:
         raise CfxError("libcfx.so ABI version mismatch")
     if hasattr(lib, "cfx_dev_stamps"):                               # the developer library: its extra entry points too
         for name, res, args in DEV_SYMBOLS:

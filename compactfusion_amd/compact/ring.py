@@ -85,7 +85,7 @@ def compact_fwd(q, k, v, dropout_p=0, softmax_scale=None, causal=True, window_si
         dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
         key = (mod_idx, id(group) if group is not None else None)
         st = _steady.get(key)
-        if st is not None and st.ex.lane and st.ex.plan is not None and not lanes.on_compute_stream(dev):
+        if st is not None and st.ex.lane and not lanes.on_compute_stream(dev):
             # steady layer: ONE flag word does both jobs - "K,V exist", published by the caller's stream (what cfx_plan_lane_begin does on
             # the compute stream when the caller is there already), is also what the compute lane waits for before it goes on.  The
             # compute lane runs neither a wait-for-fork nor a publish kernel of its own in front of the local attention block.
@@ -130,7 +130,7 @@ _lane_ok = {}        # (device, id(group)) -> world size >= 2 and the lane's str
 
 
 def _auto_lane(q, group) -> bool:
-    if _settings.get("lane") == "off" or _settings.get("ring_exchange_stream") not in ("auto", "lane") or _schedule(q) != "gather":
+    if _settings.get("lane") == "off" or _settings.get("ring_exchange_stream") == "xlayer" or _schedule(q) != "gather":
         return False
     if torch.cuda.is_current_stream_capturing():
         return False                           # the lane's flag kernels spin on words another stream writes: not capturable - the one-op path is
@@ -255,6 +255,7 @@ _prebegun = {}           # (layer, group) -> the lane epoch compact_fwd already 
 class _SteadyLayer:
     """What `_gather_schedule` established for a layer, frozen: valid while the config object, the state arena generation, the
     codec and the tensor geometry stay what they were (any change falls back to the general path, which re-binds)."""
+    _fast = None                 # `_fast_ok`'s answer, once asked
 
     def __init__(self, ex, q, k, v, ctype, cfg, rank, world):
         cache = compact_cache()
@@ -262,9 +263,8 @@ class _SteadyLayer:
         self.qs, self.ks, self.vs, self.device = q.shape, k.shape, v.shape, q.device
         self.gen, self.cver, self.sig = cm._generation, cache.version, ex.sig
         self.flags = (cfg.error_feedback, cfg.log_compress_stats, cfg.check_cache_consistency, cfg.simulate_compress, cfg.compress_residual)
-        self.N, self.C = cm._nc_shape(k.shape)
-        self.kk, self.vk = ex.kkeys[rank], ex.vkeys[rank]
         self.last_key = ex.vkeys[ex.peers[-1]]
+        self._peers = [(s, kk, vv) for s, (kk, vv) in enumerate(ex.peer_views, start=1)]      # (ring step, K, V) of the peer blocks
         self._key = None             # set by whoever files the layer under _steady
 
     def matches(self, q, k, v, ctype, cfg, causal, dropout_p) -> bool:
@@ -284,9 +284,8 @@ class _SteadyLayer:
     def _fast_ok(self, q) -> bool:
         """The lean host path applies when the fused SDPA op takes this shape and returns the layouts the native merge reads
         (decided once per layer by trying it)."""
-        ok = getattr(self, "_fast", None)
-        if ok is not None:
-            return ok
+        if self._fast is not None:
+            return self._fast
         self._fast = False
         try:
             if q.dtype == torch.float16 and q.shape[-1] % 8 == 0 and q.shape[-1] <= 512 and q.dim() == 4:
@@ -298,145 +297,86 @@ class _SteadyLayer:
                         and r[0].data_ptr() % 16 == 0):
                     dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
                     self._sdpa, self._merge, self._ctx = sdpa, _lib.load().cfx_attn_merge_wait, codecs.context(dev)
-                    self._peer_t = [(kk.transpose(1, 2), vv.transpose(1, 2)) for kk, vv in self.ex.peer_views]
+                    self._peer_t = [(s, kk.transpose(1, 2), vv.transpose(1, 2)) for s, kk, vv in self._peers]
                     self._fast = True
         except (RuntimeError, NotImplementedError):
             self._fast = False
         return self._fast
 
     def run(self, q, k, v, softmax_scale):
-        ex = self.ex
+        ex, xop = self.ex, self.ex.xop
         sh = torch.cuda.current_stream(q.device).cuda_stream
-        if ex.xop is not None:
-            # ONE native call: the layer's whole exchange on this stream, then the blocks over own K,V and the peers' states
-            xop = ex.xop
-            epoch = None
-            if xop.lowrank and xop.lane_capable():
-                from .. import lanes
-                dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
-                if lanes.on_compute_stream(dev):
-                    # low-rank family on the lane: the factor chain + publish-and-wait here, the peers' reconstructions on the exchange lane
-                    epoch = xop.run(k, v, sh, lane=True)
-                else:
-                    xop.run(k, v, sh)
-            else:
-                xop.run(k, v, sh)
-            cm._current_cache_key = self.last_key
-            if epoch is not None:
-                return self._lowrank_lane_blocks(q, k, v, softmax_scale, sh, epoch)
-            if self._fast_ok(q):
-                sdpa, merge, ctx = self._sdpa, self._merge, self._ctx
-                B, S, H, D = q.shape
-                qt = q.transpose(1, 2)
-                res = sdpa(qt, k.transpose(1, 2), v.transpose(1, 2), 0.0, False, False, scale=softmax_scale)
-                out = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
-                lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=q.device)
-                op, lp = out.data_ptr(), lse.data_ptr()
-                first = 1
-                for kt, vt in [(None, None)] + self._peer_t:
-                    if kt is not None:
-                        res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
-                    if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, first, None, 0, sh) != 0:
-                        raise RuntimeError("cfx_attn_merge failed: " + (ex.xop.lib.cfx_last_error_string(ctx) or b"").decode())
-                    first = 0
-                return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-            bo, bl = block_attention(q, k, v, 0.0, softmax_scale, causal=False)
-            out, lse = update_out_and_lse(None, None, bo, bl)
-            for kk, vv in ex.peer_views:
-                bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
-                out, lse = update_out_and_lse(out, lse, bo, bl)
-            return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-        if ex.lane:
+        if xop is None:
             # exchange lane: ONE native call issues the layer's whole chain on the exchange stream; the compute stream never sees
             # an event - the merge launch of block s also waits (in-kernel, on a flag) for peer s+1's reconstruction
-            epoch = _prebegun.pop((self._key), None)        # (auto lane: already published, from the caller's stream, before the hand-over)
+            epoch = _prebegun.pop(self._key, None)          # (auto lane: already published, from the caller's stream, before the hand-over)
             if epoch is None:
                 epoch = ex.lane_begin(sh)                   # "K, V exist" on the compute stream ...
-            fast = self._fast_ok(q)
-            if fast:
-                # lean host path (the step is host-bound long before it is GPU-bound: 8 attention + 8 merge calls per layer): cached
-                # transposed views of the peers' states, the fused SDPA op called directly, the merge through its cached entry point
-                sdpa, merge, ctx = self._sdpa, self._merge, self._ctx
-                B, S, H, D = q.shape
-                qt = q.transpose(1, 2)
-                res = sdpa(qt, k.transpose(1, 2), v.transpose(1, 2), 0.0, False, False, scale=softmax_scale)
-                ex.run_lane_head(k, v)                     # ... the chain up to the first peer's flag is issued while the local block runs
-                cm._current_cache_key = self.last_key
-                out = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
-                lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=q.device)
-                op, lp, last = out.data_ptr(), lse.data_ptr(), self.world - 1
-                if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, 1, ex.flag_ptr(1), epoch, sh) != 0:
-                    raise RuntimeError("cfx_attn_merge_wait failed: " + (ex._lib.cfx_last_error_string(ctx) or b"").decode())
-                keep = [res]
-                for s_, (kt, vt) in enumerate(self._peer_t, start=1):
-                    res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
-                    keep.append(res)
-                    if s_ == 1:
-                        ex.run_lane_tail()                 # the rest of the chain, behind the first peer's block on the compute stream
-                    if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, 0,
-                             None if s_ == last else ex.flag_ptr(s_ + 1), epoch, sh) != 0:
-                        raise RuntimeError("cfx_attn_merge_wait failed: " + (ex._lib.cfx_last_error_string(ctx) or b"").decode())
-                return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-            bo, bl = block_attention(q, k, v, 0.0, softmax_scale, causal=False)     # ... the local block behind it ...
-            ex.run_lane(k, v, None)                        # ... and the chain's dozen launches are issued while that block runs
             cm._current_cache_key = self.last_key
-            out, lse = update_out_and_lse(None, None, bo, bl, wait=(ex.flag_ptr(1), epoch))
-            last = self.world - 1
-            for s, (kk, vv) in enumerate(ex.peer_views, start=1):
-                bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
-                out, lse = update_out_and_lse(out, lse, bo, bl, wait=None if s == last else (ex.flag_ptr(s + 1), epoch))
-            return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-        ex.run_front(k, v, sh)
-        if not self.flags[0] and not ex.plan_updates_state:    # no error feedback: the state becomes the activation (main.py:240-243)
-            cache = compact_cache()
-            cache.put(self.kk, k.view(self.N, self.C), None)
-            cache.put(self.vk, v.view(self.N, self.C), None)
-        bo, bl = block_attention(q, k, v, 0.0, softmax_scale, causal=False)
-        out, lse = update_out_and_lse(None, None, bo, bl)
-        ex.run_back(sh)
+
+            def issue(s, lean):
+                # ... and the chain's dozen launches are issued while the local block runs.  Lean: only up to the first peer's flag there,
+                # the rest behind peer 1's block - the next block reaches the compute stream without waiting for 50 us of host time
+                if s == 0 and lean:
+                    ex.run_lane_head(k, v)
+                elif s == 0:
+                    ex.run_lane(k, v, None)
+                elif s == 1 and lean:
+                    ex.run_lane_tail()
+            return self._blocks(q, k, v, softmax_scale, sh, issue, ex.flag_ptr, epoch)
+        # ONE native call: the layer's whole exchange on this stream, then the blocks over own K,V and the peers' states
+        lane = False
+        if xop.lowrank and xop.lane_capable():
+            from .. import lanes
+            dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
+            # low-rank family on the lane: the factor chain + publish-and-wait here, the peers' reconstructions on the exchange lane
+            lane = lanes.on_compute_stream(dev)
+        epoch = xop.run(k, v, sh, lane)
         cm._current_cache_key = self.last_key
-        for kk, vv in ex.peer_views:
-            bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
-            out, lse = update_out_and_lse(out, lse, bo, bl)
+        if epoch is None:
+            return self._blocks(q, k, v, softmax_scale, sh)
+        # peers 1 and 2 while the local block runs, peer s + 2 behind peer s's block
+        return self._blocks(q, k, v, softmax_scale, sh, lambda s, lean: xop.lane_chain(1, 2) if s == 0 else xop.lane_chain(s + 2, 1),
+                            xop.lane_flag, epoch)
+
+    def _blocks(self, q, k, v, softmax_scale, sh, issue=None, flag=None, epoch=0):
+        """The layer's attention blocks in ring order - own K,V, then peer s = 1 .. W-1 - merged into one running out / lse.  The lane
+        forms pass `issue` and `flag`: after block s, issue(s, lean) issues the chain launches that belong behind it, and the merge of
+        block s < W-1 also waits, inside its launch, until flag(s + 1) - peer s+1 reconstructed - has reached `epoch`.  lean
+        (`_fast_ok`): the step is host-bound long before it is GPU-bound (8 attention + 8 merge calls per layer), so the fused SDPA op
+        and the merge are called directly, on cached transposed views of the peers' states; otherwise block_attention +
+        update_out_and_lse."""
+        last = self.world - 1
+        if self._fast_ok(q):
+            sdpa, merge, ctx = self._sdpa, self._merge, self._ctx
+            B, S, H, D = q.shape
+            qt = q.transpose(1, 2)
+            out = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+            lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=q.device)
+            op, lp = out.data_ptr(), lse.data_ptr()
+            keep = []                                       # the SDPA results, held until their merges are enqueued
+            for s, kt, vt in [(0, k.transpose(1, 2), v.transpose(1, 2))] + self._peer_t:
+                res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
+                keep.append(res)
+                wait = None
+                if issue is not None:
+                    issue(s, True)
+                    if s < last:
+                        wait = flag(s + 1)
+                if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, s == 0, wait, epoch, sh) != 0:
+                    from .. import _lib
+                    raise RuntimeError("cfx_attn_merge_wait failed: " + (_lib.load().cfx_last_error_string(ctx) or b"").decode())
+        else:
+            out = lse = None
+            for s, kk, vv in [(0, k, v)] + self._peers:
+                bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
+                wait = None
+                if issue is not None:
+                    issue(s, False)
+                    if s < last:
+                        wait = (flag(s + 1), epoch)
+                out, lse = update_out_and_lse(out, lse, bo, bl, wait)
         return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-
-
-def _lowrank_lane_blocks(self, q, k, v, softmax_scale, sh, epoch):
-    """The attention blocks of a low-rank layer whose peers are being reconstructed on the exchange lane: the local block first (the
-    chain's launches are issued while it runs), then peer s's block behind a merge launch that waited in-kernel for peer s's flag."""
-    xop = self.ex.xop
-    last = self.world - 1
-    if self._fast_ok(q):
-        sdpa, merge, ctx = self._sdpa, self._merge, self._ctx
-        B, S, H, D = q.shape
-        qt = q.transpose(1, 2)
-        res = sdpa(qt, k.transpose(1, 2), v.transpose(1, 2), 0.0, False, False, scale=softmax_scale)
-        xop.lane_chain(1, 2)                           # peers 1 and 2 while the local block runs, peer s + 2 behind peer s's block
-        out = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
-        lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=q.device)
-        op, lp = out.data_ptr(), lse.data_ptr()
-        if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, 1, xop.lane_flag(1), epoch, sh) != 0:
-            raise RuntimeError("cfx_attn_merge_wait failed: " + (xop.lib.cfx_last_error_string(ctx) or b"").decode())
-        keep = [res]
-        for s_, (kt, vt) in enumerate(self._peer_t, start=1):
-            res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
-            keep.append(res)
-            xop.lane_chain(s_ + 2, 1)
-            if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, 0,
-                     None if s_ == last else xop.lane_flag(s_ + 1), epoch, sh) != 0:
-                raise RuntimeError("cfx_attn_merge_wait failed: " + (xop.lib.cfx_last_error_string(ctx) or b"").decode())
-        return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-    bo, bl = block_attention(q, k, v, 0.0, softmax_scale, causal=False)
-    xop.lane_chain(1, 2)
-    out, lse = update_out_and_lse(None, None, bo, bl, wait=(xop.lane_flag(1), epoch))
-    for s_, (kk, vv) in enumerate(self.ex.peer_views, start=1):
-        bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
-        xop.lane_chain(s_ + 2, 1)
-        out, lse = update_out_and_lse(out, lse, bo, bl, wait=None if s_ == last else (xop.lane_flag(s_ + 1), epoch))
-    return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
-
-
-_SteadyLayer._lowrank_lane_blocks = _lowrank_lane_blocks
 
 
 def _exchange_stream(device) -> "torch.cuda.Stream":
@@ -465,8 +405,7 @@ class _LayerExchange:
 
     def __init__(self, mod_idx, rank: int, world: int, slot: int, like: torch.Tensor, group=None):
         self.slot, self.world, self.rank, self.group = slot, world, rank, group
-        self.plan = None             # native per-layer plan: compress, all-gather on the exchange stream | wait, reconstruct
-        self.lane = False            # plan built for the flag-synchronised exchange lane (cfx_plan_run_lane)
+        self.plan = None             # native per-layer plan: the layer's chain on the flag-synchronised exchange lane (cfx_plan_run_lane)
         self.plan_updates_state = False   # error feedback off: the plan itself copies the activation into the state, in stream order
         self._lib = None
         self.send = torch.empty(2 * slot, dtype=torch.float16, device=like.device)
@@ -482,6 +421,11 @@ class _LayerExchange:
         self.xop = None              # the layer's exchange as ONE native op (xlayer.LayerOp): the default off the exchange lane
         self._p2p = None             # CFX_RING_P2P: {"send": own packets in IPC memory, "peer": {rank: its packets, mapped}, "flag": ptr, "peer_flag": {rank: ptr}}
         self._p2p_tried = False
+
+    @property
+    def lane(self) -> bool:
+        """The layer's exchange runs on the exchange lane: every native plan bound here is the lane's."""
+        return self.plan is not None
 
     def _p2p_setup(self):
         """CFX_RING_P2P=1 (ranks of ONE node): the packets stay in cfx_ipc_alloc memory of the rank that produced them and the peers'
@@ -544,7 +488,7 @@ class _LayerExchange:
             # the local attention block.  The states are updated in place; the consumer reads them as the peers' K,V.
             from . import xlayer
             self._drop_plan()
-            self.lane, self.plan_updates_state = False, not ef
+            self.plan_updates_state = not ef
             peers, self.peer_views = [], []
             for r in self.peers:
                 bk, bv = state(self.kkeys[r]), state(self.vkeys[r])
@@ -594,10 +538,10 @@ class _LayerExchange:
 
     def _xop_wanted(self, cid, ef: bool = True) -> bool:
         """The layer's exchange as one native op on the caller's stream - unless the caller runs on the exchange lane's compute stream
-        (then the chain runs beside the attention blocks on the CU-masked exchange stream) or asked for one of the multi-launch forms."""
+        (then the chain runs beside the attention blocks on the CU-masked exchange stream) or asked for the lane (ring_exchange_stream="lane")."""
         from . import xlayer
         from .. import lanes
-        xmode = _settings.get("ring_exchange_stream")     # auto | xlayer | lane | chain | side | main
+        xmode = _settings.get("ring_exchange_stream")     # auto | xlayer | lane
         if xmode not in ("auto", "xlayer") or not xlayer.usable(cid, self.world, self.send.is_cuda, ef=ef):
             return False
         dev = self.send.device.index if self.send.device.index is not None else torch.cuda.current_device()
@@ -627,18 +571,18 @@ class _LayerExchange:
             pass
 
     def _bind_native(self, cid, param, N, C, own, own_pkts, bases, pkts, ef):
-        """The layer's exchange as ONE native plan replayed in two host calls: [compress K,V ; all-gather on the exchange
-        stream] - local attention block - [wait ; batched reconstruction].  The collective is issued by libcfx's own
+        """The layer's exchange as ONE native plan on the exchange lane: wait for flag 0 (K,V exist) ; compress K,V ; all-gather ;
+        reconstruct peer 1 .. W-1 in the order the attention blocks visit them ; the rank's own error-feedback update ; flag W - on
+        the exchange stream, ordered with the compute stream by flags alone.  The collective is issued by libcfx's own
         communicator (the reference drives torch.distributed P2P per hop, ring.py:193-195,265-269; through torch.distributed
         the per-layer all-gather costs ~50 us of host time, more than the GPU work it overlaps)."""
         self._drop_plan()
-        self.lane = False
         self.plan_updates_state = False
         mode = _settings.get("ring_exchange")
         if mode == "torch" or not self.send.is_cuda or cid >= 100:
             return
         import ctypes
-        from .. import _lib, codecs
+        from .. import _lib, codecs, lanes
         from ..exchange import native_comm_for
         dev = self.send.device.index if self.send.device.index is not None else torch.cuda.current_device()
         p2p = self._p2p
@@ -649,31 +593,15 @@ class _LayerExchange:
         lib = self._lib = _lib.load()
         ctx = codecs.context(dev)
         plan = lib.cfx_plan_create(ctx)
-        # ONE exchange stream per device, shared by every layer's plan (a stream per plan would be a hardware queue per layer)
-        xmode = _settings.get("ring_exchange_stream")     # auto | xlayer | lane | chain | side | main
-        if xmode in ("auto", "xlayer"):
-            xmode = "lane"           # (here: the caller is on the lane's compute stream, or the shape has no layer op)
-        assert xmode in ("lane", "chain", "side", "main"), "CFX_RING_EXCHANGE_STREAM must be auto | xlayer | lane | chain | side | main"
-        self._async = xmode == "chain"
-        self.lane = xmode == "lane"
-        xs_handle = None
-        if xmode == "main":
-            assert lib.cfx_plan_set_exchange_stream(plan, 0) == 0
-        else:
-            from .. import lanes
-            # the CU-masked exchange stream when the model runs on the lane's compute stream (disjoint CU sets), else an unmasked one
-            if self.lane:
-                # flags order the two streams, so the exchange stream must OWN its hardware queue (lanes.dedicated_stream)
-                # (on the lane's compute stream: the CU-masked exchange stream.  Otherwise a high-priority pool stream: non-blocking, and
-                # high-priority streams do not share a hardware queue with normal-priority ones - a CU-masked stream would own its queue too,
-                # but hipExtStreamCreateWithCUMask makes BLOCKING streams, which synchronise implicitly with the null stream most models run on)
-                xstream = lanes.exchange_stream(dev) if lanes.on_compute_stream(dev) else _exchange_stream(self.send.device)
-            else:
-                xstream = _exchange_stream(self.send.device)
-            xs_handle = xstream.cuda_stream
-            assert lib.cfx_plan_use_exchange_stream(plan, xs_handle) == 0
-        # the compress launches run on the exchange stream in the lane / chain modes: their statistics workspace belongs to THAT stream
-        ws = codecs.workspace(cid, N, C, param, 2, dev, stream_handle=xs_handle if (self.lane or self._async) else None)
+        # ONE exchange stream per device, shared by every layer's plan (a stream per plan would be a hardware queue per layer).  Flags
+        # order the two streams, so the exchange stream must OWN its hardware queue (lanes.dedicated_stream): on the lane's compute
+        # stream the CU-masked exchange stream (disjoint CU sets).  Otherwise a high-priority pool stream: non-blocking, and
+        # high-priority streams do not share a hardware queue with normal-priority ones - a CU-masked stream would own its queue too,
+        # but hipExtStreamCreateWithCUMask makes BLOCKING streams, which synchronise implicitly with the null stream most models run on
+        xstream = lanes.exchange_stream(dev) if lanes.on_compute_stream(dev) else _exchange_stream(self.send.device)
+        assert lib.cfx_plan_use_exchange_stream(plan, xstream.cuda_stream) == 0
+        # the compress launches run on the exchange stream: their statistics workspace belongs to THAT stream
+        ws = codecs.workspace(cid, N, C, param, 2, dev, stream_handle=xstream.cuda_stream)
         self._plan_keep = (ws, list(own), list(own_pkts), list(bases), list(pkts), comm)
         # error feedback off: the state becomes the activation (main.py:240-243) - done by the compress op itself, in stream order
         # behind the statistics pass that reads the old state (a copy issued from Python on another stream would race with it)
@@ -682,7 +610,6 @@ class _LayerExchange:
         c = (_lib.CompItem * 2)(*[_lib.CompItem(own[i].data_ptr(), own[i].data_ptr(), None if ef else own[i].data_ptr(), own_pkts[i].data_ptr())
                                   for i in range(2)])
         wsp, wsn = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
-        step = codecs.CFX_MAX_BATCH
 
         def dec_items(lo, hi):
             return [_lib.DecompItem(p_.data_ptr(), b_.data_ptr(), b_.data_ptr()) for p_, b_ in zip(pkts[lo:hi], bases[lo:hi])]
@@ -700,39 +627,28 @@ class _LayerExchange:
                 return 0
             pf = (ctypes.c_void_p * (self.world - 1))(*[p2p["peer_flag"][r] + 64 for r in sorted(p2p["peer_flag"])])
             return lib.cfx_plan_add_p2p_sync(plan, p2p["flag"] + 64, self.world - 1, pf)
-        if self.lane:
-            # flags: 0 = the activations exist (set on the compute stream), s = 1..W-1 = peer of ring step s reconstructed, W = chain done
-            W = self.world
-            self._flags = lib.cfx_plan_flags(plan, W + 1)
-            ok = bool(self._flags)
-            ok = ok and lib.cfx_plan_add_flag_wait(plan, 0) == 0
-            ok = ok and lib.cfx_plan_add_compress(plan, cid, N, C, param, flags, 2, c, wsp, wsn) == 1
-            ok = ok and exchange_op() == 2
-            n_own = 2 if ef else 0                 # bases / pkts start with the rank's own K,V when error feedback is on
-            for s_ in range(1, W):                 # just in time: peer s's K,V in the order the attention blocks visit them; its flag is
-                lo = n_own + 2 * (s_ - 1)          # published by the NEXT launch of the chain as the first thing it does (no launch of its own)
-                it = dec_items(lo, lo + 2)
-                op = lib.cfx_plan_add_decompress(plan, cid, N, C, param, 2, (_lib.DecompItem * 2)(*it))
-                ok = ok and op >= 0 and (s_ == 1 or lib.cfx_plan_set_pre_flag(plan, op, s_ - 1) == 0)
-            if ef:                                 # the rank's own error-feedback update: nobody waits for it before the next step
-                it = dec_items(0, 2)
-                op = lib.cfx_plan_add_decompress(plan, cid, N, C, param, 2, (_lib.DecompItem * 2)(*it))
-                ok = ok and op >= 0 and lib.cfx_plan_set_pre_flag(plan, op, W - 1) == 0
-            else:
-                ok = ok and lib.cfx_plan_add_flag_set(plan, W - 1) >= 0
-            ok = ok and lib.cfx_plan_add_flag_set(plan, W) >= 0
-            ok = ok and done_op() >= 0
-            self._epoch = ctypes.c_uint(0)
+        # flags: 0 = the activations exist (set on the compute stream), s = 1..W-1 = peer of ring step s reconstructed, W = chain done
+        W = self.world
+        self._flags = lib.cfx_plan_flags(plan, W + 1)
+        ok = bool(self._flags)
+        ok = ok and lib.cfx_plan_add_flag_wait(plan, 0) == 0
+        ok = ok and lib.cfx_plan_add_compress(plan, cid, N, C, param, flags, 2, c, wsp, wsn) == 1
+        ok = ok and exchange_op() == 2
+        n_own = 2 if ef else 0                 # bases / pkts start with the rank's own K,V when error feedback is on
+        for s_ in range(1, W):                 # just in time: peer s's K,V in the order the attention blocks visit them; its flag is
+            lo = n_own + 2 * (s_ - 1)          # published by the NEXT launch of the chain as the first thing it does (no launch of its own)
+            it = dec_items(lo, lo + 2)
+            op = lib.cfx_plan_add_decompress(plan, cid, N, C, param, 2, (_lib.DecompItem * 2)(*it))
+            ok = ok and op >= 0 and (s_ == 1 or lib.cfx_plan_set_pre_flag(plan, op, s_ - 1) == 0)
+        if ef:                                 # the rank's own error-feedback update: nobody waits for it before the next step
+            it = dec_items(0, 2)
+            op = lib.cfx_plan_add_decompress(plan, cid, N, C, param, 2, (_lib.DecompItem * 2)(*it))
+            ok = ok and op >= 0 and lib.cfx_plan_set_pre_flag(plan, op, W - 1) == 0
         else:
-            ok = lib.cfx_plan_add_compress(plan, cid, N, C, param, flags, 2, c, wsp, wsn) == 0
-            g0 = exchange_op()
-            # (front = ops [0, 2), back = the rest: with the collective the wait op is op 2; the publish-and-wait op needs none, and
-            # run_back then starts at the first reconstruction - a no-op flag set keeps the indices the same)
-            ok = ok and g0 == 1 and (lib.cfx_plan_add_wait(plan, g0) if not p2p else lib.cfx_plan_add_p2p_sync(plan, p2p["flag"] + 96, 0, None)) == 2
-            for i in range(0, len(bases), step):
-                items = dec_items(i, i + step)
-                ok = ok and lib.cfx_plan_add_decompress(plan, cid, N, C, param, len(items), (_lib.DecompItem * len(items))(*items)) >= 0
-            ok = ok and done_op() >= 0
+            ok = ok and lib.cfx_plan_add_flag_set(plan, W - 1) >= 0
+        ok = ok and lib.cfx_plan_add_flag_set(plan, W) >= 0
+        ok = ok and done_op() >= 0
+        self._epoch = ctypes.c_uint(0)
         ok = ok and lib.cfx_plan_finalize(plan) == 0
         if not ok:
             lib.cfx_plan_destroy(plan)
@@ -778,36 +694,18 @@ class _LayerExchange:
         if self.xop is not None:
             self.xop.run(k, v, sh)
             return
-        if self.lane:
-            # (two calls: cfx_plan_run_lane takes compute_stream = NULL to mean "cfx_plan_lane_begin was already called", and the
-            # legacy default stream IS the NULL handle - the ready flag would never be launched and the chain's wait would compare
-            # against a stale epoch: K,V read before the compute stream has produced them)
-            self.lane_begin(sh)
-            self._last_epoch = self.run_lane(k, v, None)
-            return
-        self._xs[0], self._xs[1] = k.data_ptr(), v.data_ptr()
-        if self._async:
-            # the whole chain - compress, all-gather, reconstruction - on the exchange stream, beside the local attention block
-            rc = self._lib.cfx_plan_run_async(self.plan, 0, self._n_ops, self._xs, 2, sh)
-        else:
-            rc = self._lib.cfx_plan_run_x(self.plan, 0, 2, self._xs, 2, sh)
-        if rc != 0:
-            raise RuntimeError("native exchange (compress + all-gather) failed: " + (self._lib.cfx_last_error_string(self._ctx) or b"").decode())
+        # (two calls: cfx_plan_run_lane takes compute_stream = NULL to mean "cfx_plan_lane_begin was already called", and the
+        # legacy default stream IS the NULL handle - the ready flag would never be launched and the chain's wait would compare
+        # against a stale epoch: K,V read before the compute stream has produced them)
+        self.lane_begin(sh)
+        self._last_epoch = self.run_lane(k, v, None)
 
     def run_back(self, sh):
         if self.xop is not None:
             return                    # (the layer op reconstructed every peer in front of the local block, in stream order)
-        if self.lane:
-            # general path: one wait for the whole chain (the steady-state lane waits per peer, inside the merge launches)
-            from .attention import flag_wait
-            flag_wait((self.flag_ptr(self.world), self._last_epoch), self.send.device)
-            return
-        if self._async:
-            rc = self._lib.cfx_plan_join(self.plan, sh)
-        else:
-            rc = self._lib.cfx_plan_run(self.plan, 2, self._n_ops - 2, sh)
-        if rc != 0:
-            raise RuntimeError("native exchange (wait + reconstruct) failed: " + (self._lib.cfx_last_error_string(self._ctx) or b"").decode())
+        # general path: one wait for the whole chain (the steady-state lane waits per peer, inside the merge launches)
+        from .attention import flag_wait
+        flag_wait((self.flag_ptr(self.world), self._last_epoch), self.send.device)
 
 
 def _layer_exchange(mod_idx, rank: int, world: int, slot: int, like: torch.Tensor, group=None) -> _LayerExchange:

@@ -13,10 +13,14 @@ setting                env var                       values / meaning
 exchange               CFX_EXCHANGE                  auto | p2p | rccl | torch - transport of the one-op layer exchange (compact/xlayer.py)
 ring_schedule          CFX_RING_SCHEDULE             auto | gather | relay - exchange schedule of compact_fwd (auto: gather on a GPU)
 ring_exchange          CFX_RING_EXCHANGE             auto | native | torch - who issues the collective of the multi-launch schedules
-ring_exchange_stream   CFX_RING_EXCHANGE_STREAM      auto | xlayer | lane | chain | side | main - where a layer's exchange chain runs
+ring_exchange_stream   CFX_RING_EXCHANGE_STREAM      auto | xlayer | lane - where a layer's exchange runs: auto = the flag-ordered chain on the
+                                                     exchange lane when the caller is on (or is put on) the lane's compute stream, else
+                                                     the one-op layer exchange on the caller's stream; xlayer = always the layer op;
+                                                     lane = always the chain on the exchange lane
 ring_p2p               CFX_RING_P2P                  (unset) | 0 | 1 - 1: the multi-launch chain reads packets in place through IPC mappings too;
                                                      0: no peer-to-peer transport at all (the layer op starts at rccl)
-ring_exchange_priority CFX_RING_EXCHANGE_PRIORITY    priority of the (unmasked) exchange stream of the event-ordered schedules (-1)
+ring_exchange_priority CFX_RING_EXCHANGE_PRIORITY    priority of the unmasked exchange stream: the lane's when the caller is off its compute stream,
+                                                     the torch all-gather's (-1)
 lane                   CFX_LANE                      auto | sticky | off - how compact_fwd gets onto the exchange lane when the caller is not
                                                      on it already: auto = for the duration of the call (forked from and joined to the
                                                      caller's stream with flag kernels: the model's other kernels keep the caller's stream);
@@ -40,7 +44,7 @@ _SETTINGS = {
     "exchange": ("CFX_EXCHANGE", "auto", ("auto", "p2p", "rccl", "torch")),
     "ring_schedule": ("CFX_RING_SCHEDULE", "auto", ("auto", "gather", "relay")),
     "ring_exchange": ("CFX_RING_EXCHANGE", "auto", ("auto", "native", "torch")),
-    "ring_exchange_stream": ("CFX_RING_EXCHANGE_STREAM", "auto", ("auto", "xlayer", "lane", "chain", "side", "main")),
+    "ring_exchange_stream": ("CFX_RING_EXCHANGE_STREAM", "auto", ("auto", "xlayer", "lane")),
     "ring_p2p": ("CFX_RING_P2P", "", None),
     "ring_exchange_priority": ("CFX_RING_EXCHANGE_PRIORITY", "-1", None),
     "lane": ("CFX_LANE", "auto", ("auto", "sticky", "off")),

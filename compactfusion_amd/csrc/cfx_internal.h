@@ -243,7 +243,6 @@ struct cfx_plan {
     int n, cap;
     hipStream_t side;     // exchange stream (created on first all-gather op, or the caller's: side_owned = false)
     bool side_owned;
-    hipEvent_t ev_fork, ev_join;   // cfx_plan_run_async / cfx_plan_join
     int side_mode;        // 0: issue collectives on the main stream (no cross-stream events), 1: side stream, 2: prioritised side stream
     void* pipe_ws;        // cfx_plan_run_pipelined: two statistics workspaces of CFX_MAX_BATCH tensors each (stats of unit
     size_t pipe_ws_bytes; //   t runs beside the finalize of unit t-1)

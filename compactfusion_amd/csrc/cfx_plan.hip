@@ -143,7 +143,6 @@ cfx_plan* cfx_plan_create(cfx_ctx* ctx) {
     p->n = p->cap = 0;
     p->side = nullptr;
     p->side_owned = true;
-    p->ev_fork = p->ev_join = nullptr;
     p->pipe_ws = nullptr;
     p->pipe_ws_bytes = 0;
     p->sched = nullptr;
@@ -191,8 +190,6 @@ void cfx_plan_destroy(cfx_plan* p) {
         if (p->ops[i].ev_done) (void)hipEventDestroy(p->ops[i].ev_done);
     }
     if (p->side && p->side_owned) (void)hipStreamDestroy(p->side);
-    if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-    if (p->ev_join) (void)hipEventDestroy(p->ev_join);
     if (p->pipe_ws) (void)hipFree(p->pipe_ws);
     if (p->flags) (void)hipFree(p->flags);
     if (p->p2p_sink) (void)hipFree(p->p2p_sink);
@@ -559,7 +556,7 @@ static int launch_flag_exchange(cfx_plan* p, const PlanOp* o, hipStream_t s, con
     return check_launch(p->ctx, what);
 }
 
-// `inline_exchange`: exchange ops run in order on `stream` itself whatever the plan's exchange-stream mode (cfx_plan_run_async:
+// `inline_exchange`: exchange ops run in order on `stream` itself whatever the plan's exchange-stream mode (cfx_plan_run_lane:
 // the whole range already runs on the exchange stream).
 static int plan_run_impl(cfx_plan* p, int first_op, int n_ops, void* stream, bool inline_exchange) {
     if (!p) return CFX_ERR_NULL;
@@ -687,40 +684,6 @@ static int plan_run_impl(cfx_plan* p, int first_op, int n_ops, void* stream, boo
 }
 
 int cfx_plan_run(cfx_plan* p, int first_op, int n_ops, void* stream) { return plan_run_impl(p, first_op, n_ops, stream, false); }
-
-// The whole op range on the plan's EXCHANGE stream, forked off `main_stream` and joined back later: everything a layer's exchange
-// does - compress, collective, reconstruction - runs beside what the caller enqueues on `main_stream` in between (the local
-// attention block).  cfx_plan_join makes `main_stream` wait for the range.  The activations (xs, see cfx_plan_run_x) must stay
-// alive until the join.
-int cfx_plan_run_async(cfx_plan* p, int first_op, int n_ops, const void* const* xs, int n_xs, void* main_stream) {
-    if (!p) return CFX_ERR_NULL;
-    if (!p->side) return fail(p->ctx, CFX_ERR_BATCH, "plan: run_async needs an exchange stream (cfx_plan_use_exchange_stream, or mode 1 / 2 and an exchange op)");
-    if (!p->ev_fork && (hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
-        return fail(p->ctx, CFX_ERR_LAUNCH, "plan: cannot create events");
-    if (first_op < 0 || n_ops < 0 || first_op + n_ops > p->n) return fail(p->ctx, CFX_ERR_BATCH, "plan: op range out of bounds");
-    if (n_xs > 0) {
-        if (!xs) return CFX_ERR_NULL;
-        int op = first_op;
-        while (op < first_op + n_ops && !takes_activations(p->ops[op].kind)) ++op;
-        if (op == first_op + n_ops || p->ops[op].batch != n_xs) return fail(p->ctx, CFX_ERR_BATCH, "plan: run_async needs a compress op with n_xs items in the range");
-        for (int i = 0; i < n_xs; ++i) {
-            if (!xs[i] || !AL16(xs[i])) return fail(p->ctx, CFX_ERR_ALIGN, "plan: activations must be non-null and 16-byte aligned");
-            p->ops[op].c[i].x = xs[i];
-        }
-    }
-    if (hipEventRecord(p->ev_fork, (hipStream_t)main_stream) != hipSuccess || hipStreamWaitEvent(p->side, p->ev_fork, 0) != hipSuccess)
-        return fail(p->ctx, CFX_ERR_LAUNCH, "plan: fork failed");
-    const int rc = plan_run_impl(p, first_op, n_ops, (void*)p->side, true);
-    if (hipEventRecord(p->ev_join, p->side) != hipSuccess) return fail(p->ctx, CFX_ERR_LAUNCH, "plan: join event failed");
-    return rc;
-}
-
-int cfx_plan_join(cfx_plan* p, void* main_stream) {
-    if (!p) return CFX_ERR_NULL;
-    if (!p->ev_join) return fail(p->ctx, CFX_ERR_BATCH, "plan: join without run_async");
-    return hipStreamWaitEvent((hipStream_t)main_stream, p->ev_join, 0) == hipSuccess ? CFX_OK : fail(p->ctx, CFX_ERR_LAUNCH, "plan: join failed");
-}
 
 // ---- exchange lane (see the flag kernels above) -------------------------------------------------------------------------
 void* cfx_plan_flags(cfx_plan* p, int n) {

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define CFX_ABI_VERSION 1
+#define CFX_ABI_VERSION 2
 #define CFX_MAX_BATCH 16
 
 typedef struct cfx_ctx cfx_ctx;
@@ -326,7 +326,7 @@ int       cfx_plan_add_wait(cfx_plan* plan, int gather_op);
  * nothing moves, the exchange stream runs one relay kernel (wait + set).  Any codec; the one-launch form exists for the 1-bit codec.
  * When the one-launch form is not available (codec or shape
  * without it, a run stream masked below 128 CUs, the legacy NULL stream beside a BLOCKING exchange stream - every CU-masked stream is
- * one -, cfx_hw_queues_ok() == 0, cfx_plan_run_async / _lane) the op runs as compress ; all-gather ; reconstruct in order - same results.  The exchange stream must own a hardware queue (see "Exchange lane" below): the plan creates a
+ * one -, cfx_hw_queues_ok() == 0, cfx_plan_run_lane) the op runs as compress ; all-gather ; reconstruct in order - same results.  The exchange stream must own a hardware queue (see "Exchange lane" below): the plan creates a
  * CU-masked one unless cfx_plan_use_exchange_stream supplied it (one stream should serve all plans).  A gate that never opens times
  * out like any flag wait (CFX_ERR_GATE at the next call).
  * With more than one rank the collective is a KERNEL that has to be placed while the reconstruction workgroups hold their CUs: the
@@ -384,13 +384,6 @@ int       cfx_plan_run(cfx_plan* plan, int first_op, int n_ops, void* stream);
 /* cfx_plan_run after re-pointing the n_xs activations of the first compress op of the range (cfx_plan_set_input + run in
  * one host call: what a layer's K,V hand-over costs). */
 int       cfx_plan_run_x(cfx_plan* plan, int first_op, int n_ops, const void* const* xs, int n_xs, void* stream);
-/* The op range - compress, collective, reconstruction - on the plan's EXCHANGE stream, forked off `main_stream` (an event)
- * so that it runs beside what the caller enqueues on `main_stream` next: the local attention block, which needs none of it
- * (reference ring.py:207-209).  Exchange ops of the range run in order on that stream; wait ops are no-ops.
- * cfx_plan_join(plan, main_stream) makes `main_stream` wait for the range (before the first peer block).  Two host calls per
- * layer.  The activations must stay alive until the join. */
-int       cfx_plan_run_async(cfx_plan* plan, int first_op, int n_ops, const void* const* xs, int n_xs, void* main_stream);
-int       cfx_plan_join(cfx_plan* plan, void* main_stream);
 /* Exchange lane: the layer's chain (compress, collective, per-peer reconstruction) on its own - normally CU-masked - stream, ordered
  * with the compute stream ONLY through flag words in device memory (no events: a cross-stream event hop costs ~14 us of idle queue
  * time on MI355X / ROCm 7.2, a flag written by one stream's kernel and polled by the other's ~1.7 us; tools/lane_probe.hip).

@@ -23,7 +23,7 @@ def test_header_symbols_exported_and_bound():
         assert hasattr(lib, sym), f"{sym} declared in include/cfx.h but not exported by libcfx.so"
         assert sym in bound, f"{sym} declared in include/cfx.h but not bound in compactfusion_amd/_lib.py"
     assert bound <= set(declared), bound - set(declared)
-    assert lib.cfx_abi_version() == 1
+    assert lib.cfx_abi_version() == 2
 
 
 def test_packet_bytes_match_oracle_and_reference_arithmetic():

@@ -224,15 +224,19 @@ def test_plugin_call_low_rank_family_one_native_call_per_layer(loop8, api, codec
     assert lib.cfx_gate_errors(ctx) == 0
 
 
-@pytest.mark.parametrize("codec,rank", [("LOW_RANK", 8), ("LOW_RANK_Q", 32)])
-@pytest.mark.parametrize("lane", ["auto", "sticky"])
+@pytest.mark.parametrize("lane,codec,rank", [("auto", "LOW_RANK", 8), ("auto", "LOW_RANK_Q", 32), ("sticky", "LOW_RANK", 8),
+                                             ("sticky", "LOW_RANK_Q", 32), ("auto-generic", "LOW_RANK", 8)])
 def test_low_rank_layer_beside_the_attention_blocks(loop8, monkeypatch, codec, rank, lane):
     """Protocol 2 for the low-rank family (round 6): with the lane at its default, a steady LOW_RANK / LOW_RANK_Q layer keeps its factor
     chain (+ publish-and-wait) on the compute lane and leaves the peers' reconstructions to the exchange lane, peer by peer behind flags
     the merge launches wait for (xlayer.LayerOp.run(lane=True) / lane_chain).  Against the same steps with the lane off (the one-call
     layer op on the caller's stream): every state bit for bit (same pinned start matrix: the chain's sums do not depend on the stream),
-    the attention output to merge-order tolerance; and the launches say the lane form ran: one reconstruction launch per peer."""
+    the attention output to merge-order tolerance; and the launches say the lane form ran: one reconstruction launch per peer.
+    "auto-generic": both runs take the steady layer's generic block path (block_attention + update_out_and_lse instead of the lean one)."""
     ring, cm, xlayer = loop8
+    if lane == "auto-generic":
+        monkeypatch.setattr(ring._SteadyLayer, "_fast_ok", lambda self, q: False)
+        lane = "auto"
     from compactfusion_amd import _lib, codecs as K, lanes
     from compactfusion_amd.compact import COMPACT_COMPRESS_TYPE as T, CompactConfig, lowrank
     lib, ctx = _lib.load(), K.context(0)

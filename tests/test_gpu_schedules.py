@@ -210,11 +210,11 @@ def test_long_context_attention_hook_on_gpu(tmp_path, ulysses, ring, compact_on)
 
 
 # ---- the native per-layer chain (libcfx communicator, exchange stream, steady-state lane) with 4 logical ranks looped back ----
-def test_native_exchange_chain_in_compact_fwd_vs_oracle(tmp_path):
-    """compact_fwd's gather schedule with the layer's whole exchange issued natively (cfx_plan_run_async / cfx_plan_join, the
-    library-owned communicator = tests/fake_rccl in loop-back mode: every logical peer is this rank).  Every peer state and the
-    rank's own error-feedback state must equal the oracle's replay of the rank's own shard, over enough steps to cover the
-    general path (binds the plan), and the steady-state lane."""
+def test_native_exchange_lane_in_compact_fwd_vs_oracle(tmp_path):
+    """compact_fwd's gather schedule with the layer's whole exchange issued natively on the exchange lane (cfx_plan_run_lane, the
+    library-owned communicator = tests/fake_rccl in loop-back mode: every logical peer is this rank), the caller on its own stream.  Every
+    peer state and the rank's own error-feedback state must equal the oracle's replay of the rank's own shard, over enough steps to cover
+    the general path (binds the plan), and the steady-state lane."""
     import ctypes
     import sys
     import tempfile
@@ -245,44 +245,45 @@ def test_native_exchange_chain_in_compact_fwd_vs_oracle(tmp_path):
     ring.dist.all_gather_into_tensor = lambda recv, send, group=None: recv.view(Wl, -1).copy_(send.view(1, -1).expand(Wl, -1))
     collector.init(collector.Collector(tempfile.mkdtemp(), enabled=False))
     try:
-        for xmode in ("chain", "side"):
-            os.environ["CFX_RING_EXCHANGE"] = "native"
-            os.environ["CFX_RING_EXCHANGE_STREAM"] = xmode
-            exchange.set_comm_factory(LoopComm)
-            ring._xbuf.clear(); ring._steady.clear()
-            cm.compact_init(CompactConfig(enabled=True, compress_func=lambda l, s: T.WARMUP if s == 0 else T.BINARY, comp_rank=-1,
-                                          residual=1, ef=True, fastpath=True))
-            qs = [W.drift(7 + l, (B, S, Hh, Dh), STEPS) for l in range(L)]
-            ks = [W.drift(17 + l, (B, S, Hh, Dh), STEPS) for l in range(L)]
-            vs = [W.drift(27 + l, (B, S, Hh, Dh), STEPS) for l in range(L)]
-            steady_hits = 0
-            for step in range(STEPS):
-                cm.compact_set_step(step)
-                for l in range(L):
-                    st = ring._steady.get((l, None))
-                    out, lse, _ = ring.compact_fwd(qs[l][step].cuda(), ks[l][step].cuda(), vs[l][step].cuda(), causal=False, mod_idx=l, current_iter=step)
-                    steady_hits += int(st is not None)
-            torch.cuda.synchronize()
-            assert all(ex.plan is not None for ex in ring._xbuf.values() if ex.sig is not None), "the native plan was not used"
-            assert steady_hits >= L * (STEPS - 2), "the steady-state lane was not taken"
+        os.environ["CFX_RING_EXCHANGE"] = "native"
+        os.environ["CFX_RING_EXCHANGE_STREAM"] = "lane"
+        os.environ["CFX_LANE"] = "off"
+        exchange.set_comm_factory(LoopComm)
+        ring._xbuf.clear(); ring._steady.clear()
+        cm.compact_init(CompactConfig(enabled=True, compress_func=lambda l, s: T.WARMUP if s == 0 else T.BINARY, comp_rank=-1,
+                                      residual=1, ef=True, fastpath=True))
+        qs = [W.drift(7 + l, (B, S, Hh, Dh), STEPS) for l in range(L)]
+        ks = [W.drift(17 + l, (B, S, Hh, Dh), STEPS) for l in range(L)]
+        vs = [W.drift(27 + l, (B, S, Hh, Dh), STEPS) for l in range(L)]
+        steady_hits = 0
+        for step in range(STEPS):
+            cm.compact_set_step(step)
             for l in range(L):
-                wk, wv = _chain("BINARY", ks[l])[-1], _chain("BINARY", vs[l])[-1]
-                for r in range(Wl):
-                    gk = cm.compact_cache().get_base(f"{l}-{r}-k")
-                    gv = cm.compact_cache().get_base(f"{l}-{r}-v")
-                    assert np.array_equal(W.bits(gk).reshape(-1), wk.reshape(-1)), (xmode, l, r, "k")
-                    assert np.array_equal(W.bits(gv).reshape(-1), wv.reshape(-1)), (xmode, l, r, "v")
-            # the output of the last step: every block sees this rank's K,V (local exact, peers reconstructed)
-            from compactfusion_amd.compact.attention import block_attention
-            l = L - 1
-            kk = [ks[l][-1].cuda()] + [cm.compact_cache().get_base(f"{l}-{r}-k").view(B, S, Hh, Dh) for r in range(1, Wl)]
-            vv = [vs[l][-1].cuda()] + [cm.compact_cache().get_base(f"{l}-{r}-v").view(B, S, Hh, Dh) for r in range(1, Wl)]
-            ref, _ = block_attention(qs[l][-1].cuda(), torch.cat(kk, 1), torch.cat(vv, 1), 0.0, None, causal=False)
-            torch.testing.assert_close(out.float(), ref.float(), rtol=2e-3, atol=2e-3)
+                st = ring._steady.get((l, None))
+                out, lse, _ = ring.compact_fwd(qs[l][step].cuda(), ks[l][step].cuda(), vs[l][step].cuda(), causal=False, mod_idx=l, current_iter=step)
+                steady_hits += int(st is not None)
+        torch.cuda.synchronize()
+        assert all(ex.plan is not None for ex in ring._xbuf.values() if ex.sig is not None), "the native plan was not used"
+        assert steady_hits >= L * (STEPS - 2), "the steady-state lane was not taken"
+        for l in range(L):
+            wk, wv = _chain("BINARY", ks[l])[-1], _chain("BINARY", vs[l])[-1]
+            for r in range(Wl):
+                gk = cm.compact_cache().get_base(f"{l}-{r}-k")
+                gv = cm.compact_cache().get_base(f"{l}-{r}-v")
+                assert np.array_equal(W.bits(gk).reshape(-1), wk.reshape(-1)), (l, r, "k")
+                assert np.array_equal(W.bits(gv).reshape(-1), wv.reshape(-1)), (l, r, "v")
+        # the output of the last step: every block sees this rank's K,V (local exact, peers reconstructed)
+        from compactfusion_amd.compact.attention import block_attention
+        l = L - 1
+        kk = [ks[l][-1].cuda()] + [cm.compact_cache().get_base(f"{l}-{r}-k").view(B, S, Hh, Dh) for r in range(1, Wl)]
+        vv = [vs[l][-1].cuda()] + [cm.compact_cache().get_base(f"{l}-{r}-v").view(B, S, Hh, Dh) for r in range(1, Wl)]
+        ref, _ = block_attention(qs[l][-1].cuda(), torch.cat(kk, 1), torch.cat(vv, 1), 0.0, None, causal=False)
+        torch.testing.assert_close(out.float(), ref.float(), rtol=2e-3, atol=2e-3)
     finally:
         ring.dist.get_rank, ring.dist.get_world_size, ring.dist.all_gather_into_tensor = saved
         exchange.set_comm_factory(None)
-        os.environ.pop("CFX_RING_EXCHANGE", None); os.environ.pop("CFX_RING_EXCHANGE_STREAM", None)
+        for v in ("CFX_RING_EXCHANGE", "CFX_RING_EXCHANGE_STREAM", "CFX_LANE"):
+            os.environ.pop(v, None)
         ring._xbuf.clear(); ring._steady.clear()
 
 

@@ -448,6 +448,9 @@ def test_configure_is_the_one_place_for_host_switches(monkeypatch):
     assert config.get("exchange") == "rccl"                      # back to the environment layer
     with pytest.raises(ValueError):
         compactfusion_amd.configure(lane="sometimes")
+    for retired in ("chain", "side", "main"):                     # the event-ordered exchange forms are gone
+        with pytest.raises(ValueError):
+            compactfusion_amd.configure(ring_exchange_stream=retired)
     with pytest.raises(TypeError):
         compactfusion_amd.configure(no_such_switch=1)
     monkeypatch.setenv("CFX_LANE", "bogus")

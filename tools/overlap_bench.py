@@ -15,9 +15,6 @@ must hide under the local attention block).  Legs, all on the same inputs:
   layer_op       configure(lane="off") (round 4's default): the layer's exchange as ONE native op (compact/xlayer.py: one codec launch gated on the
                  packets' arrival) on the model's own stream, in front of the local attention block - nothing overlaps, one launch per layer
   lane_unmasked  the same flags, but the model on an ordinary stream and the chain on an unmasked exchange stream
-  native         round 2's schedule: the chain on the exchange stream, forked and joined with EVENTS (cfx_plan_run_async + cfx_plan_join)
-  native_gather_only_on_side   as round 1 scheduled it: compress and reconstruction on the compute stream, only the collective beside
-                 the local block
   torchdist      compact_fwd with the collective issued from Python (what round 1 did; the loop-back copy stands in for
                  torch.distributed.all_gather_into_tensor, whose ~50 us of host time per call is NOT included here)
 Reported: wall ms/step, host issue ms/step, exposed exchange = leg - attention, host us/layer (by difference of legs: noisy;
@@ -39,7 +36,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--layers", type=int, default=57)
 ap.add_argument("--json", default=None)
-ap.add_argument("--quick", action="store_true", help="only the attention, lane and event-fork legs")
+ap.add_argument("--quick", action="store_true", help="without the torchdist leg")
 ap.add_argument("--quiet", action="store_true", help="do not print the JSON (bench.py runs this file as a child process and reads --json)")
 ap.add_argument("--legs", default=None, help="comma-separated subset of the legs (for kernel traces); default all")
 ap.add_argument("--preset", default="binary", choices=["binary", "int2", "lowrank8", "lowrank16", "lowrankq32"],
@@ -137,7 +134,7 @@ def fwd(i):
         ring.compact_fwd(qs[l], ks[i & 1][l], vs[i & 1][l], causal=False, mod_idx=l, current_iter=i)
 
 
-def init(mode, xstream="chain", lane_mode="off"):
+def init(mode, xstream="lane", lane_mode="off"):
     os.environ["CFX_RING_EXCHANGE"] = mode
     os.environ["CFX_RING_EXCHANGE_STREAM"] = xstream
     os.environ["CFX_LANE"] = lane_mode
@@ -171,16 +168,16 @@ comp_stream = lanes.compute_stream(0)
 # (`default` / `sticky` come LAST: they bring two more streams into the process, and with more streams than hardware queues
 # (GPU_MAX_HW_QUEUES = 8) the flag-ordered legacy legs that follow share queues with something and are time-sliced - measured 36-43 ms per
 # step for `lane_unmasked` / `native` behind them, 23.2 / 23.9 in a process of their own)
-ALL = ["attention_on_compute_lane", "lane", "attention_distinct_kv_on_compute_lane", "attention", "layer_op", "lane_unmasked", "native", "native_gather_only_on_side", "torchdist", "default", "sticky"]
+ALL = ["attention_on_compute_lane", "lane", "attention_distinct_kv_on_compute_lane", "attention", "layer_op", "lane_unmasked", "torchdist", "default", "sticky"]
 if args.preset != "binary" and not args.legs:
     ALL = ["attention_on_compute_lane", "attention", "layer_op", "default", "sticky"]
 legs = [x for x in (args.legs.split(",") if args.legs else ALL) if x]
 assert all(x in ALL for x in legs), f"legs must be among {ALL}"
 if args.quick:
-    legs = [x for x in legs if x not in ("native_gather_only_on_side", "torchdist")]
+    legs = [x for x in legs if x != "torchdist"]
 res = {}
 default_path = None
-lane_used = native_used = None
+lane_used = None
 _side = None
 for leg in legs:
     if leg == "attention_on_compute_lane":
@@ -239,13 +236,6 @@ for leg in legs:
     elif leg == "lane_unmasked":
         init("native", "lane")
         res[leg] = timed(fwd, 3)
-    elif leg == "native":
-        init("native", "chain")
-        native_used = all(ex.plan is not None for ex in ring._xbuf.values() if ex.sig is not None)
-        res[leg] = timed(fwd, 3)
-    elif leg == "native_gather_only_on_side":
-        init("native", "side")
-        res[leg] = timed(fwd, 3)
     elif leg == "torchdist":
         init("torch")
         res[leg] = timed(fwd, 3)
@@ -285,7 +275,6 @@ out = {
     "default_path": default_path,
     "steps": args.steps,
     "lane": {"exchange_cus": lanes.lane(0).exchange_cus, "compute_cus": lanes.lane(0).compute_cus, "lane_plan_used": lane_used},
-    "native_plan_used": native_used,
     "legs_ms_per_step": {k: {"wall": round(v[0], 3), "host_issue": round(v[1], 3)} for k, v in res.items()},
     "exposed_exchange_ms_per_step": {k: round(res[k][0] - base_of(k), 3) for k in res if not k.startswith("attention") and base_of(k) is not None},
     "exposed_exchange_ms_per_step_vs_attention_over_distinct_kv": None if att_dist is None or "lane" not in res else round(res["lane"][0] - att_dist, 3),
