@@ -12,7 +12,7 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import CFX_MAX_BATCH, FLAG_NO_EF, FLAG_UPDATE_CACHE, CfxError, CompItem, DecompItem
+from ._lib import CFX_MAX_BATCH, ELEM_BF16, FLAG_NO_EF, FLAG_UPDATE_CACHE, CfxError, CompItem, DecompItem
 
 
 class Codec(IntEnum):
@@ -72,7 +72,7 @@ def _check(ctx, rc: int, what: str) -> None:
 def packet_bytes(codec: int, N: int, C: int, param: int = 0) -> int:
     n = _lib.load().cfx_packet_bytes(int(codec), N, C, param)
     if n == 0:
-        raise ValueError(f"invalid shape for codec {Codec(codec).name}: N={N} C={C} param={param}")
+        raise ValueError(f"invalid shape for codec {int(codec):#x}: N={N} C={C} param={param}")
     return n
 
 
@@ -107,9 +107,30 @@ def _stream_handle(stream: Optional[torch.cuda.Stream], device: int) -> int:
     return s.cuda_stream
 
 
-def _check_nc(t: torch.Tensor, N: int, C: int, name: str) -> None:
-    if t.dtype != torch.float16 or not t.is_contiguous() or t.numel() != N * C:
-        raise ValueError(f"{name}: expected contiguous fp16 with {N}x{C} elements, got {t.dtype} {tuple(t.shape)}")
+def _check_nc(t: torch.Tensor, N: int, C: int, name: str, dtype: torch.dtype = torch.float16) -> None:
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != N * C:
+        what = {torch.float16: "fp16", torch.bfloat16: "bf16"}[dtype]
+        raise ValueError(f"{name}: expected contiguous {what} with {N}x{C} elements, got {t.dtype} {tuple(t.shape)}")
+
+
+def elem_dtype(*tensors: Optional[torch.Tensor]) -> torch.dtype:
+    """The element type of a call, taken from its tensor operands (x, base, new_base, recon; packets are fp16-typed bytes and do not
+    count): fp16 or bf16, the same for all of them - include/cfx.h, "bf16 activations".  ValueError on anything else or on a mix."""
+    dt = None
+    for t in tensors:
+        if t is None:
+            continue
+        if t.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"expected fp16 or bf16 tensors, got {t.dtype}")
+        if dt is not None and t.dtype != dt:
+            raise ValueError(f"mixed element types in one call: {dt} and {t.dtype} (all of x, base, new_base, recon are fp16, or all bf16)")
+        dt = t.dtype
+    return torch.float16 if dt is None else dt
+
+
+def codec_arg(codec: int, dtype: torch.dtype) -> int:
+    """The C-ABI's `codec` argument for tensors of `dtype`: the codec id, with CFX_ELEM_BF16 for bf16."""
+    return int(codec) | (ELEM_BF16 if dtype == torch.bfloat16 else 0)
 
 
 def compress_batch(codec: int, xs: Sequence[torch.Tensor], bases: Sequence[Optional[torch.Tensor]],
@@ -123,19 +144,20 @@ def compress_batch(codec: int, xs: Sequence[torch.Tensor], bases: Sequence[Optio
     dev = _device_index(xs[0])
     ctx = context(dev)
     items = (CompItem * B)()
+    dt = elem_dtype(*xs, *bases, *new_bases)
     for i in range(B):
-        _check_nc(xs[i], N, C, "x")
+        _check_nc(xs[i], N, C, "x", dt)
         if bases[i] is not None:
-            _check_nc(bases[i], N, C, "base")
+            _check_nc(bases[i], N, C, "base", dt)
         if new_bases[i] is not None:
-            _check_nc(new_bases[i], N, C, "new_base")
+            _check_nc(new_bases[i], N, C, "new_base", dt)
         _device_index(packets[i])
         items[i] = CompItem(_ptr(xs[i]), _ptr(bases[i]), _ptr(new_bases[i]), _ptr(packets[i]))
     flags = (FLAG_UPDATE_CACHE if update_cache else 0) | (0 if ef else FLAG_NO_EF)
     sh = _stream_handle(stream, dev)
     if ws is None:
         ws = workspace(codec, N, C, param, B, dev, sh)
-    rc = _lib.load().cfx_compress_batch(ctx, int(codec), N, C, param, flags, B, items,
+    rc = _lib.load().cfx_compress_batch(ctx, codec_arg(codec, dt), N, C, param, flags, B, items,
                                         _ptr(ws), 0 if ws is None else ws.numel(), sh)
     _check(ctx, rc, "cfx_compress_batch")
 
@@ -150,45 +172,48 @@ def decompress_batch(codec: int, packets: Sequence[torch.Tensor], bases: Sequenc
     dev = _device_index(recons[0])
     ctx = context(dev)
     items = (DecompItem * B)()
+    dt = elem_dtype(*recons, *bases)
     for i in range(B):
-        _check_nc(recons[i], N, C, "recon")
+        _check_nc(recons[i], N, C, "recon", dt)
         if bases[i] is not None:
-            _check_nc(bases[i], N, C, "base")
+            _check_nc(bases[i], N, C, "base", dt)
         _device_index(packets[i])
         items[i] = DecompItem(_ptr(packets[i]), _ptr(bases[i]), _ptr(recons[i]))
-    rc = _lib.load().cfx_decompress_batch(ctx, int(codec), N, C, param, B, items, _stream_handle(stream, dev))
+    rc = _lib.load().cfx_decompress_batch(ctx, codec_arg(codec, dt), N, C, param, B, items, _stream_handle(stream, dev))
     _check(ctx, rc, "cfx_decompress_batch")
 
 
 def prepare_compress(codec: int, bases: Sequence[Optional[torch.Tensor]], new_bases: Sequence[Optional[torch.Tensor]],
                      packets: Sequence[torch.Tensor], N: int, C: int, param: int = 0, update_cache: bool = True,
-                     ef: bool = True) -> Callable[[Sequence[torch.Tensor]], None]:
+                     ef: bool = True, dtype: Optional[torch.dtype] = None) -> Callable[[Sequence[torch.Tensor]], None]:
     """`compress_batch` with the state / packet operands bound once (persistent arena and exchange buffers): the
     returned `run(xs, stream_handle=None)` only patches the activation pointers into a cached item array - the
-    per-call host cost of the exchange hot loop.  The bound tensors are kept alive by the closure."""
+    per-call host cost of the exchange hot loop.  The bound tensors are kept alive by the closure.  The element type is the bound
+    states' (`dtype` when there are none: fp16 by default); the activations of every run must have it."""
     B = len(packets)
     if not (1 <= B <= CFX_MAX_BATCH):
         raise ValueError(f"batch {B} out of range 1..{CFX_MAX_BATCH}")
     dev = _device_index(packets[0])
     ctx = context(dev)
     items = (CompItem * B)()
+    dt = elem_dtype(*bases, *(new_bases if update_cache else ())) if dtype is None else dtype
     for i in range(B):
         if bases[i] is not None:
-            _check_nc(bases[i], N, C, "base")
+            _check_nc(bases[i], N, C, "base", dt)
         if new_bases[i] is not None and update_cache:
-            _check_nc(new_bases[i], N, C, "new_base")
+            _check_nc(new_bases[i], N, C, "new_base", dt)
         _device_index(packets[i])
         items[i] = CompItem(None, _ptr(bases[i]), _ptr(new_bases[i]) if update_cache else None, _ptr(packets[i]))
     flags = (FLAG_UPDATE_CACHE if update_cache else 0) | (0 if ef else FLAG_NO_EF)
     fn = _lib.load().cfx_compress_batch
     keep = (list(bases), list(new_bases), list(packets))
-    codec = int(codec)
+    codec = codec_arg(codec, dt)
     ws_by_stream = {}        # the workspace belongs to the stream the call is launched on, looked up at call time
 
     def run(xs: Sequence[torch.Tensor], stream_handle: Optional[int] = None) -> None:
         assert len(xs) == B and keep
         for i in range(B):
-            _check_nc(xs[i], N, C, "x")
+            _check_nc(xs[i], N, C, "x", dt)
             items[i].x = xs[i].data_ptr()
         sh = torch.cuda.current_stream(dev).cuda_stream if stream_handle is None else stream_handle
         w = ws_by_stream.get(sh)
@@ -208,15 +233,16 @@ def prepare_decompress(codec: int, packets: Sequence[torch.Tensor], bases: Seque
     dev = _device_index(recons[0])
     ctx = context(dev)
     items = (DecompItem * B)()
+    dt = elem_dtype(*recons, *bases)
     for i in range(B):
-        _check_nc(recons[i], N, C, "recon")
+        _check_nc(recons[i], N, C, "recon", dt)
         if bases[i] is not None:
-            _check_nc(bases[i], N, C, "base")
+            _check_nc(bases[i], N, C, "base", dt)
         _device_index(packets[i])
         items[i] = DecompItem(_ptr(packets[i]), _ptr(bases[i]), _ptr(recons[i]))
     fn = _lib.load().cfx_decompress_batch
     keep = (list(packets), list(bases), list(recons))
-    codec = int(codec)
+    codec = codec_arg(codec, dt)
 
     def run(stream_handle: Optional[int] = None) -> None:
         assert keep
@@ -228,19 +254,21 @@ def prepare_decompress(codec: int, packets: Sequence[torch.Tensor], bases: Seque
 def compress(codec: int, x: torch.Tensor, base: Optional[torch.Tensor], N: int, C: int, param: int = 0,
              update_cache: bool = True, ef: bool = True, new_base: Optional[torch.Tensor] = None,
              packet: Optional[torch.Tensor] = None):
-    """Single tensor convenience.  Returns (packet fp16 1-D, new_base | None)."""
+    """Single tensor convenience.  Returns (packet fp16 1-D, new_base | None); new_base has x's element type (fp16 or bf16)."""
     if packet is None:
         packet = torch.empty(packet_halves(codec, N, C, param), dtype=torch.float16, device=x.device)
     if update_cache and new_base is None:
-        new_base = torch.empty((N, C), dtype=torch.float16, device=x.device)
+        new_base = torch.empty((N, C), dtype=x.dtype, device=x.device)
     compress_batch(codec, [x], [base], [new_base if update_cache else None], [packet], N, C, param, update_cache, ef)
     return packet, (new_base if update_cache else None)
 
 
 def decompress(codec: int, packet: torch.Tensor, base: Optional[torch.Tensor], N: int, C: int, param: int = 0,
                recon: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """recon = base + decode(packet).  An allocated recon takes the base's element type; without a base it is fp16 (the packet does
+    not say what its sender's activations were: pass a bf16 `recon` to get the bf16 rounding of the contract)."""
     if recon is None:
-        recon = torch.empty((N, C), dtype=torch.float16, device=packet.device)
+        recon = torch.empty((N, C), dtype=torch.float16 if base is None else base.dtype, device=packet.device)
     if packet.data_ptr() % 16:
         packet = packet.clone()   # the kernels want a 16-byte aligned packet; a slice of a gather buffer may not be
     decompress_batch(codec, [packet], [base], [recon], N, C, param)

@@ -5,7 +5,10 @@ int2_dequant_fastpath :745-811 and their `sim_*` twins) with identical argument 
 Each quantiser is ONE call into libcfx.so that produces the wire packet `[codes | U | V]`; the returned `packed`,
 `scale_u`, `scale_v` tensors are VIEWS into that packet (no copies), `new_base` is a fresh (N, C) tensor as in the
 reference.  The dequantisers rebuild a packet from the three parts (a copy - the state-machine API in `main.py`
-passes whole packets and never pays it)."""
+passes whole packets and never pays it).
+
+x and base are fp16, or both bf16 (rank -1 only): new_base / the reconstruction then are bf16 too, packed / scale_u / scale_v stay what
+they are for fp16 (include/cfx.h, "bf16 activations").  Mixed element types raise ValueError."""
 from __future__ import annotations
 
 import torch
@@ -16,8 +19,9 @@ from ..prof import Profiler
 _BIN, _I2 = int(codecs.Codec.BINARY), int(codecs.Codec.INT2)
 
 
-def _check(x, base):
-    assert x.dtype == torch.half and base.dtype == torch.half
+def _check(x, base, rank=-1):
+    if codecs.elem_dtype(x, base) == torch.bfloat16 and rank != -1:
+        raise NotImplementedError(f"torch.bfloat16 activations are not supported with rank {rank} scales (the rank-K 1-bit codec is fp16 only)")
     assert x.ndim == 2 and base.ndim == 2 and x.shape == base.shape
 
 
@@ -32,7 +36,7 @@ def _quant(cid, per_byte, x, base, update_cache):
 
 
 def _dequant(cid, per_byte, packed, u, v, base):
-    assert packed.dtype == torch.uint8 and u.dtype == torch.half and v.dtype == torch.half and base.dtype == torch.half
+    assert packed.dtype == torch.uint8 and u.dtype == torch.half and v.dtype == torch.half and base.dtype in (torch.half, torch.bfloat16)
     N, Cp = packed.shape
     C = Cp * per_byte
     assert u.shape == (N, 1) and v.shape == (C, 1), "scale shapes must be U(N,1), V(C,1) (comp_rank = -1)"
@@ -45,7 +49,7 @@ def _dequant(cid, per_byte, packed, u, v, base):
 def binary_quant_fastpath(x_tensor_nc: torch.Tensor, base_tensor_nc: torch.Tensor, rank: int, update_cache: bool):
     """-> packed (N, C//8) uint8, scale_u (N,K), scale_v (C,K), new_base (N,C) | None.   rank -1 (K = 1: mean scales) or 1..32."""
     assert rank >= 1 or rank == -1, "Rank must be >= 1 or -1"
-    _check(x_tensor_nc, base_tensor_nc)
+    _check(x_tensor_nc, base_tensor_nc, rank)
     if rank != -1:
         # scales = rank-K factors of |x - base| (fastpath.py:186-200: subspace_iter on the absolute residual): -> U (N, K), V (C, K)
         from . import lowrank
@@ -63,6 +67,8 @@ def binary_quant_fastpath(x_tensor_nc: torch.Tensor, base_tensor_nc: torch.Tenso
 def binary_dequant_fastpath(packed: torch.Tensor, scale_u_nk: torch.Tensor, scale_v_ck: torch.Tensor, base_nc: torch.Tensor):
     K = scale_u_nk.shape[1]
     if K > 1 or scale_v_ck.shape[1] > 1:              # rank-K scales (the rank is inferred from the scales, fastpath.py:400-404)
+        if base_nc.dtype == torch.bfloat16:
+            raise NotImplementedError("torch.bfloat16 activations are not supported with rank-K scales (the rank-K 1-bit codec is fp16 only)")
         N, Cp = packed.shape
         C = Cp * 8
         assert scale_u_nk.shape == (N, K) and scale_v_ck.shape == (C, K) and base_nc.shape == (N, C)

@@ -19,6 +19,12 @@ Semantics kept from the reference (file:line = xfuser/compact/main.py):
   when error feedback is on, base <- act otherwise (:227-243, :373-377); residual 2 adds the decayed second-order
   predictor (:244-266, :378-384; `cfx_residual2_delta` / `cfx_residual2_update` around the codec, states in place); `simulate` ships the dequantised tensor (:117-119, :126-127); the fastpath accepts
   only BINARY / INT2 (:131, :277).
+
+Activations may be fp16 or bf16.  bf16 (what FLUX, CogVideoX, HunyuanVideo run in) is served by the 1-bit and 2-bit codecs - plus WARMUP and
+IDENTITY - with first-order or no residuals: states and reconstructions are bf16, the residual and the wire stay fp16 (include/cfx.h,
+"bf16 activations").  Every other combination with bf16 raises NotImplementedError before any state is touched
+(`_check_bf16`); nothing is ever cast behind the caller's back.  `compact_decompress` with residual 0 has no state to take the element
+type from and returns fp16; the gather entry points pass their activation's type down.
 """
 from __future__ import annotations
 
@@ -163,6 +169,28 @@ def _native(compress_type: T) -> Tuple[int, int]:
     raise ValueError(f"Invalid compress_type value: {compress_type}")
 
 
+def _check_bf16(dtype, compress_type: T) -> None:
+    """bf16 activations: the supported matrix, checked before any state is touched.  Never a silent cast."""
+    if dtype != torch.bfloat16:
+        return
+    cfg = _config
+
+    def no(option: str):
+        raise NotImplementedError(f"torch.bfloat16 activations are not supported with {option}: bf16 runs with BINARY (comp_rank -1) / INT2 / "
+                                  "WARMUP / IDENTITY, compress_residual 0 or 1, no simulation, no quantized cache - use fp16 activations "
+                                  "for anything else")
+    if compress_type not in (T.BINARY, T.INT2, T.WARMUP, T.IDENTITY):
+        no(f"compress type {getattr(compress_type, 'name', compress_type)}")
+    if compress_type == T.BINARY and cfg.comp_rank is not None and cfg.comp_rank != -1:
+        no(f"BINARY with comp_rank {cfg.comp_rank} (rank-K scales)")
+    if cfg.simulate_compress and compress_type not in (T.IDENTITY, T.WARMUP):
+        no(f"simulate_compress and compress type {compress_type.name}")
+    if cfg.compress_residual == 2:
+        no("compress_residual 2")
+    if cfg.quantized_cache or (_cache is not None and _cache.quantize):
+        no("quantized_cache")
+
+
 def compact_bind_packet(cache_key, buffer: torch.Tensor) -> None:
     """Extension: make `compact_compress(cache_key, ...)` write its packet straight into `buffer` (a 1-D fp16 view,
     16-byte aligned, of exactly the packet length) - e.g. a slot of an exchange buffer - instead of a private one."""
@@ -242,6 +270,7 @@ def compact_compress(cache_key, x: torch.Tensor, compress_type: COMPACT_COMPRESS
     _current_cache_key = cache_key
     assert x.is_contiguous()
     assert _config.enabled
+    _check_bf16(x.dtype, compress_type)
     original_shape = x.shape
     x = x.view(_nc_shape(x.shape))
     N, C = x.shape
@@ -333,12 +362,24 @@ def compact_compress(cache_key, x: torch.Tensor, compress_type: COMPACT_COMPRESS
 @Profiler.prof_func("compact.compact_decompress")
 def compact_decompress(cache_key, compressed: torch.Tensor, compress_type: COMPACT_COMPRESS_TYPE, shape: tuple,
                        update_cache: bool = False):
+    """The reconstruction has the element type of the key's state (fp16 or bf16); with compress_residual 0 there is none and it is
+    fp16 - a packet does not say what its sender's activations were (the gather entry points know and say so: `_decompress`)."""
+    return _decompress(cache_key, compressed, compress_type, shape, update_cache, None)
+
+
+def _decompress(cache_key, compressed: torch.Tensor, compress_type: COMPACT_COMPRESS_TYPE, shape: tuple, update_cache: bool, dtype):
+    """`compact_decompress`; dtype: the activations' element type where the caller knows it (None: the state's, fp16 without one)."""
     global _current_cache_key
     _current_cache_key = cache_key
     assert _config.enabled
     original_shape = tuple(shape)
     N, C = _nc_shape(shape)
     cfg, cache = _config, _cache
+    if compress_type != T.WARMUP:
+        if dtype is None and cfg.compress_residual != 0 and not cache.quantize:
+            held = cache.base.get(cache_key)
+            dtype = None if held is None else held.dtype
+        _check_bf16(dtype, compress_type)
 
     if compress_type == T.WARMUP:
         val = compressed.view(N, C)
@@ -378,7 +419,7 @@ def compact_decompress(cache_key, compressed: torch.Tensor, compress_type: COMPA
     assert compressed.numel() == expected, \
         f"Mismatch in compressed tensor size: expected {expected}, got {compressed.numel()}, Shape (N,C)=({N},{C})"
     if cfg.compress_residual == 0:
-        out = torch.empty((N, C), dtype=torch.float16, device=compressed.device)
+        out = torch.empty((N, C), dtype=dtype or torch.float16, device=compressed.device)
         _codec_decompress(cid, param, compressed, None, out)
         return out.view(original_shape)
     base = cache.get_base(cache_key)
@@ -388,19 +429,19 @@ def compact_decompress(cache_key, compressed: torch.Tensor, compress_type: COMPA
             _codec_decompress(cid, param, compressed, base, base)       # in place: recon IS the new base
             cache.put(cache_key, base, None)
             return base.view(original_shape)
-        out = _buf(cache_key, "recon", N * C, base).view(N, C)
+        out = _buf(cache_key, "recon", N * C, base, base.dtype).view(N, C)
         _codec_decompress(cid, param, compressed, base, out)
         return out.view(original_shape)
     dbase = cache.get_delta_base(cache_key)
     assert dbase is not None, f"no second-order state for key {cache_key}: residual 2 needs two WARMUP steps"
-    recv = _buf(cache_key, "recv", N * C, base).view(N, C)
+    recv = _buf(cache_key, "recv", N * C, base, base.dtype).view(N, C)
     _codec_decompress(cid, param, compressed, None, recv)
     if update_cache:
         codecs.residual2_update(base, dbase, recv, base, dbase, cfg.delta_decay_factor)         # in place on the arena
         cache.put(cache_key, base, dbase)
         return base.view(original_shape)
-    rec = torch.empty((N, C), dtype=torch.float16, device=compressed.device)
-    codecs.residual2_update(base, dbase, recv, rec, _buf(cache_key, "ndb", N * C, base).view(N, C), cfg.delta_decay_factor)
+    rec = torch.empty((N, C), dtype=base.dtype, device=compressed.device)
+    codecs.residual2_update(base, dbase, recv, rec, _buf(cache_key, "ndb", N * C, base, base.dtype).view(N, C), cfg.delta_decay_factor)
     return rec.view(original_shape)
 
 
@@ -427,7 +468,7 @@ def compact_all_gather(tag, x: torch.Tensor, comp_type: COMPACT_COMPRESS_TYPE, g
         dist.all_gather_into_tensor(recvbuf, sendbuf, group=group)
     bufs = [recvbuf[i * slot:i * slot + flat.numel()] for i in range(world)]
     if not native_batch:
-        return [compact_decompress(f"{tag}-{i}", bufs[i], comp_type, x.shape, update_cache=True) for i in range(world)]
+        return [_decompress(f"{tag}-{i}", bufs[i], comp_type, x.shape, True, x.dtype) for i in range(world)]
     # batched native reconstruction: one launch for all W shards, in place on the state arena
     global _current_cache_key
     N, C = _nc_shape(x.shape)
@@ -624,6 +665,10 @@ def compact_all_gather_kv(tag_k, tag_v, k: torch.Tensor, v: torch.Tensor, comp_t
     `displaced=True` selects the one-step-stale variant described in `_KVExchange`."""
     assert _config.enabled
     cfg = _config
+    if k.dtype == torch.bfloat16 or v.dtype == torch.bfloat16:
+        if k.dtype != v.dtype:
+            raise ValueError(f"K and V of different element types: {k.dtype}, {v.dtype}")
+        _check_bf16(k.dtype, comp_type)
     xkey = (tag_k, tag_v, id(group) if group is not None else None)
     ex = _kv_exchanges.get(xkey)
     # steady state of the synchronous exchange: the layer is bound to ONE native op and nothing it was bound against has changed - straight to it

@@ -207,7 +207,10 @@ def _compact_ring_fwd(q, k, v, dropout_p=0, softmax_scale=None, causal=True, win
     rank, world = comm.rank, comm.world_size
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     ctype = compact_config().compress_func(mod_idx, current_iter)
-    kshape, vshape = k.shape, v.shape
+    if k.dtype != v.dtype:
+        raise ValueError(f"K and V of different element types: {k.dtype}, {v.dtype}")
+    cm._check_bf16(k.dtype, ctype)             # bf16 K,V: the 1-bit / 2-bit codecs, first-order or no residual - refused before any state moves
+    kshape, vshape, act_dtype = k.shape, v.shape, k.dtype
     kkey = lambda r: f"{mod_idx}-{r % world}-k"   # noqa: E731
     vkey = lambda r: f"{mod_idx}-{r % world}-v"   # noqa: E731
 
@@ -229,8 +232,8 @@ def _compact_ring_fwd(q, k, v, dropout_p=0, softmax_scale=None, causal=True, win
                 comm.commit()
             if step != 0:
                 src = rank - step
-                k = compact_decompress(kkey(src), k_send, ctype, kshape, update_cache=True).contiguous()
-                v = compact_decompress(vkey(src), v_send, ctype, vshape, update_cache=True).contiguous()
+                k = cm._decompress(kkey(src), k_send, ctype, kshape, True, act_dtype).contiguous()
+                v = cm._decompress(vkey(src), v_send, ctype, vshape, True, act_dtype).contiguous()
             out, lse = attend(out, lse, k, v, step)
             if step + 1 != world:
                 with Profiler.scope("compact.ring.wait"):
@@ -261,6 +264,7 @@ class _SteadyLayer:
         cache = compact_cache()
         self.ex, self.ctype, self.cfg, self.rank, self.world = ex, ctype, cfg, rank, world
         self.qs, self.ks, self.vs, self.device = q.shape, k.shape, v.shape, q.device
+        self.dt = k.dtype            # the element type the layer's states and native ops are bound to
         self.gen, self.cver, self.sig = cm._generation, cache.version, ex.sig
         self.flags = (cfg.error_feedback, cfg.log_compress_stats, cfg.check_cache_consistency, cfg.simulate_compress, cfg.compress_residual)
         self.last_key = ex.vkeys[ex.peers[-1]]
@@ -272,7 +276,7 @@ class _SteadyLayer:
         ex = self.ex
         if ctype is not self.ctype or cfg is not self.cfg or causal or dropout_p or (ex.plan is None and ex.xop is None):
             return False
-        if q.shape != self.qs or k.shape != self.ks or v.shape != self.vs or q.device != self.device:
+        if q.shape != self.qs or k.shape != self.ks or v.shape != self.vs or q.device != self.device or k.dtype != self.dt or v.dtype != self.dt:
             return False
         if cm._generation != self.gen or cm._cache.version != self.cver or ex.sig is not self.sig:
             return False
@@ -593,6 +597,7 @@ class _LayerExchange:
         lib = self._lib = _lib.load()
         ctx = codecs.context(dev)
         plan = lib.cfx_plan_create(ctx)
+        cid = codecs.codec_arg(cid, codecs.elem_dtype(*own, *bases))     # (bf16 states: CFX_ELEM_BF16 on every op of the chain)
         # ONE exchange stream per device, shared by every layer's plan (a stream per plan would be a hardware queue per layer).  Flags
         # order the two streams, so the exchange stream must OWN its hardware queue (lanes.dedicated_stream): on the lane's compute
         # stream the CU-masked exchange stream (disjoint CU sets).  Otherwise a high-priority pool stream: non-blocking, and
@@ -766,8 +771,9 @@ def _gather_schedule(q, k, v, ctype, mod_idx, rank, world, group, kkey, vkey, at
         pk = compact_compress(kkey(rank), k, ctype, update_cache=True)
         pv = compact_compress(vkey(rank), v, ctype, update_cache=True)
         if pk.reshape(-1).data_ptr() != send.data_ptr():
-            send[:n_half].copy_(pk.reshape(-1))
-            send[slot:slot + n_half].copy_(pv.reshape(-1))
+            # (a raw shard - WARMUP, simulation - travels as its own 16-bit words: a bf16 one is never converted on the way)
+            send[:n_half].view(pk.dtype).copy_(pk.reshape(-1))
+            send[slot:slot + n_half].view(pv.dtype).copy_(pv.reshape(-1))
     # exchange on the side stream, overlapped with the local attention block
     if fast and native_x:
         pass
@@ -828,7 +834,8 @@ def _gather_schedule(q, k, v, ctype, mod_idx, rank, world, group, kkey, vkey, at
             kk = compact_cache().get_base(kkey(r)).view(kshape)
             vv = compact_cache().get_base(vkey(r)).view(vshape)
         else:
-            kk = compact_decompress(kkey(r), ex.packet(r, 0, n_half), ctype, kshape, update_cache=True).contiguous()
-            vv = compact_decompress(vkey(r), ex.packet(r, 1, n_half), ctype, vshape, update_cache=True).contiguous()
+            wire = k.dtype if (warm or cfg.simulate_compress) else torch.float16
+            kk = cm._decompress(kkey(r), ex.packet(r, 0, n_half).view(wire), ctype, kshape, True, k.dtype).contiguous()
+            vv = cm._decompress(vkey(r), ex.packet(r, 1, n_half).view(wire), ctype, vshape, True, k.dtype).contiguous()
         out, lse = attend(out, lse, kk, vv, step)
     return out, lse

@@ -97,7 +97,8 @@ class CompactConfig:
 
 
 class CompactCache:
-    """key -> persistent (N, C) fp16 state buffer (+ optional second-order `delta_base`).
+    """key -> persistent (N, C) state buffer in the activations' element type - fp16, or bf16 with the 1-bit / 2-bit exchange - (+ optional
+    second-order `delta_base`).
 
     `put` copies into the key's arena buffer unless it is handed that very buffer (what the in-place kernels do), so
     pointers stay stable for the life of the generation; tensors returned by `get_base` alias the arena and are valid
@@ -116,7 +117,7 @@ class CompactCache:
 
     # -- arena ----------------------------------------------------------------------------------------------
     def arena(self, key: str, like: torch.Tensor) -> torch.Tensor:
-        """The key's persistent buffer, (re)allocated to match `like` (shape (N, C), fp16, same device)."""
+        """The key's persistent buffer, (re)allocated to match `like` (shape (N, C), same element type, same device)."""
         buf = self.base.get(key)
         if buf is None or buf.shape != like.shape or buf.device != like.device or buf.dtype != like.dtype:
             buf = torch.empty(like.shape, dtype=like.dtype, device=like.device)

@@ -396,6 +396,13 @@ class LayerOp:
         # per tensor and one reconstruction per peer tensor from Python (16 launches and 0.44 ms of host time per FLUX layer).
         self.lowrank = self.cid >= 100
         self.quantized = self.cid == 102
+        # element type of the layer: the states' (fp16, or bf16 with the 1-bit / 2-bit codecs - include/cfx.h, "bf16 activations"); the
+        # activations of every run must have it.  `cabi` is the C-ABI's codec argument: the id, with CFX_ELEM_BF16 for bf16
+        self.dtype = codecs.elem_dtype(*self.own, *[t for _, ks, vs in self.peers for t in (ks, vs)])
+        if self.dtype == torch.bfloat16 and self.cid not in (int(codecs.Codec.BINARY), int(codecs.Codec.INT2)):
+            raise NotImplementedError(f"torch.bfloat16 activations are not supported with codec id {self.cid} in the layer exchange op "
+                                      "(bf16 runs with the 1-bit and 2-bit codecs)")
+        self.cabi = self.cid if self.lowrank else codecs.codec_arg(self.cid, self.dtype)
         if self.lowrank:
             assert self.cid in (101, 102) and own_update == "ef", "the low-rank layer op exists with error feedback only"
             self.pkt_bytes = 2 * codecs.lr_packet_halves(self.quantized, N, C, self.param)
@@ -492,7 +499,7 @@ class LayerOp:
 
     def _build(self, sh: int):
         lib, ctx = self.lib, self.ctx
-        cid, param, N, C = self.cid, self.param, self.N, self.C
+        cid, param, N, C = self.cabi, self.param, self.N, self.C
         plan = lib.cfx_plan_create(ctx)
         self._check(plan, "cfx_plan_create")
         if self.lowrank:
@@ -626,6 +633,8 @@ class LayerOp:
         runs on `sh`; the publish-and-wait and the reconstructions of the peers are left to `lane_chain()`, which puts them on the exchange
         lane behind a flag published here - the epoch the caller's merge launches wait for is returned.  None: everything ran in stream
         order on `sh` (a validated execution, another transport), nothing is left to wait for."""
+        if k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError(f"the layer exchange op is bound to {self.dtype} states, got K {k.dtype} / V {v.dtype}: mixed element types")
         ent = self._plans.get(sh)
         if ent is None:
             ent = self._build(sh)
@@ -817,7 +826,7 @@ class LayerOp:
                     bad = 1
                 for kv, got in ((0, ks), (1, vs)):
                     again = torch.empty_like(got)
-                    if lib.cfx_decompress(ctx, self.cid, reg.packet(r, op, kv), snap[2 + 2 * i + kv].data_ptr(), again.data_ptr(), self.N, self.C,
+                    if lib.cfx_decompress(ctx, self.cabi, reg.packet(r, op, kv), snap[2 + 2 * i + kv].data_ptr(), again.data_ptr(), self.N, self.C,
                                           self.param, sh) != 0:
                         bad = 1
                     stream.synchronize()

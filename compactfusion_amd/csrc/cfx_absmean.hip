@@ -38,7 +38,7 @@ extern "C" CFX_HIDDEN void cfx_i_lr_factor_offsets(int N, int C, int rank, size_
 // TAG (the layer launches): the partials go out as tagged words (put_tagged).  The sign bits a reconstruction workgroup will read are
 // drained BEFORE the tile's column partials are stored: the gate only opens once every column block's V job has read every tile's
 // column partials, so a tile's bits are in memory by then; its row partials need not wait for anything.
-template <bool EMIT_BITS, int US, bool WT = false, int NW = WAVES, bool PUB = false, bool KEEP = false, bool TAG = false>
+template <bool EMIT_BITS, int US, bool WT = false, int NW = WAVES, bool PUB = false, bool KEEP = false, bool TAG = false, class E = ElemF16>
 __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int N, int C, int R, int CB, int bx, int by,
                                                    u64* rowpart, u64 (*sm)[TILE_C], Probe probe = Probe(),
                                                    h16x8* xk = nullptr, h16x8* bk = nullptr, TagArena ta = TagArena()) {
@@ -81,7 +81,7 @@ __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int 
         for (int j = 0; j < US; ++j) {
             const int rr = r + NW * j;
             if (rr < t.r1 && t.act) {
-                const h16x8 d = xv[j] - bv[j];
+                const h16x8 d = el_diff<E>(xv[j], bv[j]);
                 const h16x8 a = habs8(d);
                 unsigned byte = 0;
                 double rsum = 0.0;
@@ -149,10 +149,10 @@ __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int 
 #undef SSTAMP
 }
 
-template <bool EMIT_BITS>
+template <bool EMIT_BITS, class E>
 __global__ __launch_bounds__(NTHR) void k_absmean_stats(BatchC batch, int N, int C, int R, u64* ws, size_t ws_stride) {
     __shared__ u64 sm[WAVES][TILE_C];
-    absmean_stats_body<EMIT_BITS, UNROLL_S>(batch.it[blockIdx.z], N, C, R, gridDim.x, blockIdx.x, blockIdx.y, ws + (size_t)blockIdx.z * ws_stride, sm);
+    absmean_stats_body<EMIT_BITS, UNROLL_S, false, WAVES, false, false, false, E>(batch.it[blockIdx.z], N, C, R, gridDim.x, blockIdx.x, blockIdx.y, ws + (size_t)blockIdx.z * ws_stride, sm);
 }
 
 // finalize: U[n] = rowmean/mean(rowmean) (1-bit, fastpath.py:164-165) or rowmean/(mean+1e-6) (2-bit, :619-622);
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(1024) void k_absmean_finalize(BatchC batch, int N, 
 // UPDATE_CACHE branch of _binary_quant_fastpath (fastpath.py:88-120): out = base + (2b-1)*fp16(u[n]*v[c])
 // ---------------------------------------------------------------------------------------------------
 // UN = rows a wave keeps in flight (2 on the whole chip; 4 on a CU-masked lane, where bytes in flight per CU bound the rate)
-template <int NW = WAVES, int UN = UNROLL>
+template <int NW = WAVES, int UN = UNROLL, class E = ElemF16>
 __device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, int N, int C, int R, int tile_x, int tile_y) {
     const TileCoord t = tile_coord_at(tile_x, tile_y, N, C, R);
     const unsigned char* pk = (const unsigned char*)it.packet;
@@ -278,17 +278,17 @@ __device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, i
 #pragma unroll
                 for (int i = 0; i < 8; ++i) sb[i] ^= ((by[j] >> i) & 1u) ? (u16)0 : (u16)0x8000;   // (2b-1)*s
                 const h16x8 recv = __builtin_bit_cast(h16x8, sb);
-                st8nt(out + (size_t)rr * C + t.c, base ? (bv[j] + recv) : recv);
+                st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bv[j], recv));
             }
         }
     }
 }
 
-template <int UN>
+template <int UN, class E>
 __global__ __launch_bounds__(NTHR) void k_binary_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
     // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
     if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
-    binary_dequant_body<WAVES, UN>(batch.it[blockIdx.z], N, C, R, blockIdx.x, blockIdx.y);
+    binary_dequant_body<WAVES, UN, E>(batch.it[blockIdx.z], N, C, R, blockIdx.x, blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -444,7 +444,7 @@ __device__ __forceinline__ bool scales_from_tagged(const TagArena& ta, int N, in
 #ifndef ONEBIT_D_TAGGED
 #define ONEBIT_D_TAGGED 0
 #endif
-template <int NW, int KR, int KL, bool ST>
+template <int NW, int KR, int KL, bool ST, class E = ElemF16>
 __device__ __forceinline__ void binary_dequant_gated_body(const cfx_decomp_item& it, int N, int C, int R, int tile_x, int tile_y,
                                                          unsigned* gate, unsigned expect, unsigned* err, long long timeout, u32x4* lds,
                                                          Probe probe = Probe(), bool remote = false, bool tagged = false, TagArena ta = TagArena(),
@@ -522,7 +522,7 @@ __device__ __forceinline__ void binary_dequant_gated_body(const cfx_decomp_item&
             h16x8 bj = (h16x8)(h16)0;
             if (j < KR) bj = bv[j < KR ? j : 0];
             else if (base) bj = __builtin_bit_cast(h16x8, lds[(j - KR) * (NW * 64) + threadIdx.x]);
-            st8nt(out + (size_t)rr * C + t.c, base ? (bj + recv) : recv);
+            st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bj, recv));
         }
     }
     GSTAMP(4);
@@ -814,7 +814,7 @@ __device__ __forceinline__ void absmean_tagged_jobs(const cfx_comp_item& it, int
 // What a statistics workgroup of the 2-bit layer launch does with its own tile once the scales exist (R == FUSED_NW * US, the tile
 // of x and of the state still in registers): wait for gate 1, quantise (the codes depend on the scales), publish the codes
 // write-through, error feedback, one arrival on gate 2 - the arithmetic of k_int2_quant without reading x and the state again.
-template <int US>
+template <int US, class E = ElemF16>
 __device__ __forceinline__ void own_tile_finish(const cfx_comp_item& it, int N, int C, int R, int bx, int by, int flags, const h16x8* xk,
                                                 const h16x8* bk, unsigned* gate1, unsigned expect1, unsigned* gate2, unsigned expect2,
                                                 unsigned* err, long long timeout, unsigned char* smw, const TagArena& ta, u16* s16) {
@@ -838,7 +838,7 @@ __device__ __forceinline__ void own_tile_finish(const cfx_comp_item& it, int N, 
         const h16 tk = hfrom((u16)__builtin_amdgcn_readlane((int)ul, j));
         codes[j] = 0;
         if (rr < t.r1 && t.act) {
-            const h16x8 d = xk[j] - bk[j];
+            const h16x8 d = el_diff<E>(xk[j], bk[j]);
             const h16x8 thr = ch8 * tk;                                      // fastpath.py:536
             const h16x8 a = habs8(d);
             unsigned code = 0;
@@ -873,7 +873,7 @@ __device__ __forceinline__ void own_tile_finish(const cfx_comp_item& it, int N, 
             const h16 tk = hfrom((u16)__builtin_amdgcn_readlane((int)ul, j));
             if (rr < t.r1 && t.act) {
                 const h16x8 recv = int2_recv(codes[j], ch8 * tk);
-                st8nt(nb + (size_t)rr * C + t.c, ef ? (has_base ? (bk[j] + recv) : recv) : xk[j]);
+                st8nt(nb + (size_t)rr * C + t.c, ef ? (el_state<E>(has_base, bk[j], recv)) : xk[j]);
             }
         }
     }
@@ -881,7 +881,7 @@ __device__ __forceinline__ void own_tile_finish(const cfx_comp_item& it, int N, 
 
 // KEEP (the 2-bit layer launch): after the statistics and - for a last arriver - its jobs, the workgroup stays and quantises its own
 // tile from registers (own_tile_finish).
-template <bool EMIT_BITS, int US, bool GATED = false, bool KEEP = false>
+template <bool EMIT_BITS, int US, bool GATED = false, bool KEEP = false, class E = ElemF16>
 __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int N, int C, int R, int CB, int P, int bx, int by,
                                                    u64* rowpart, unsigned* tick, int per_byte, int eps_mode, u64 (*sm)[TILE_C], int dbg,
                                                    Probe probe, unsigned* gate = nullptr, unsigned gate_expect = 0, int flags = 0,
@@ -911,7 +911,7 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
     }
 #endif
     h16x8 xk[KEEP ? US : 1], bk[KEEP ? US : 1];
-    absmean_stats_body<EMIT_BITS, US, true, FUSED_NW, GATED, KEEP, GATED>(it, N, C, R, CB, bx, by, rowpart, sm, probe, xk, bk, ta);
+    absmean_stats_body<EMIT_BITS, US, true, FUSED_NW, GATED, KEEP, GATED, E>(it, N, C, R, CB, bx, by, rowpart, sm, probe, xk, bk, ta);
     STAMP(1);
     if constexpr (GATED) {
         // the layer launches: tagged partials, fixed reducers (absmean_tagged_jobs) - nothing to drain, no ticket to draw
@@ -980,7 +980,7 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
     }
     }
     if constexpr (KEEP)
-        own_tile_finish<US>(it, N, C, R, bx, by, flags, xk, bk, gate, gate_expect, gate2, expect2, err, timeout,
+        own_tile_finish<US, E>(it, N, C, R, bx, by, flags, xk, bk, gate, gate_expect, gate2, expect2, err, timeout,
                                        (unsigned char*)&sm[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)][0], ta, (u16*)&sm[FUSED_NW + 4][0]);
 #undef STAMP
 }
@@ -1020,7 +1020,7 @@ struct FusedArgs {
 // by itself when the developer probes' branches are compiled in and took 122 without them (same code, other schedule), so the budget is
 // stated: amdgpu_num_vgpr counts HALF registers on gfx90a+ (unified 512-entry file: LLVM doubles the request), 52 -> 104.  No spills
 // (tests/test_resource_usage.py reads the compiler's remarks: ScratchSize 0, VGPRs <= 104).
-template <bool EMIT_BITS, int US, bool GATED = false, bool ST = false>
+template <bool EMIT_BITS, int US, bool GATED, bool ST, class E>
 __global__ __launch_bounds__(FUSED_NT, GATE_WPE) __attribute__((amdgpu_num_vgpr(52))) void k_absmean_compress(BatchC batch, BatchD ride, BatchD gated, FusedArgs a) {
     __shared__ u64 sm[FUSED_NW][TILE_C];
     int b = blockIdx.x;
@@ -1028,7 +1028,7 @@ __global__ __launch_bounds__(FUSED_NT, GATE_WPE) __attribute__((amdgpu_num_vgpr(
         const int per = a.CB * a.P;
         const int z = b / per, rem = b - z * per;
         const int by = rem / a.CB;
-        absmean_fused_body<EMIT_BITS, US, GATED>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
+        absmean_fused_body<EMIT_BITS, US, GATED, false, E>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
                                                  a.tick + z * TICK_WORDS, a.per_byte, a.eps_mode, sm, a.dbg,
                                                  a.probe.of(b), a.gate, a.gate_expect, 0, nullptr, 0u, a.gate_err, a.timeout,
                                                  tag_arena_of(a.tarena, a.tarena_stride, z, a.N, a.C, a.CB, a.P, a.tag));
@@ -1047,7 +1047,7 @@ __global__ __launch_bounds__(FUSED_NT, GATE_WPE) __attribute__((amdgpu_num_vgpr(
                     const int ty = rem / a.CB;
                     const int sz = a.src[item];
                     const TagArena ta = tag_arena_of(a.tarena, a.tarena_stride, sz >= 0 ? sz : 0, a.N, a.C, a.CB, a.P, a.tag);
-                    binary_dequant_gated_body<FUSED_NW, GATE_KR, 0, ST>(gated.it[item], a.N, a.C, a.g_R, rem - ty * a.CB, ty, a.xgate ? a.xgate : a.gate,
+                    binary_dequant_gated_body<FUSED_NW, GATE_KR, 0, ST, E>(gated.it[item], a.N, a.C, a.g_R, rem - ty * a.CB, ty, a.xgate ? a.xgate : a.gate,
                                                                 a.xgate ? a.xexpect : a.gate_expect, a.gate_err, a.timeout,
                                                                 nullptr,
                                                                 a.probe.of(blockIdx.x), a.remote != 0 && sz < 0,
@@ -1060,7 +1060,7 @@ __global__ __launch_bounds__(FUSED_NT, GATE_WPE) __attribute__((amdgpu_num_vgpr(
         const int per = a.CB * a.dq_rb;
         const int item = b / per, rem = b - item * per;
         const int ty = rem / a.CB;
-        binary_dequant_body<FUSED_NW>(ride.it[item], a.N, a.C, a.dq_R, rem - ty * a.CB, ty);
+        binary_dequant_body<FUSED_NW, UNROLL, E>(ride.it[item], a.N, a.C, a.dq_R, rem - ty * a.CB, ty);
     }
 }
 
@@ -1116,6 +1116,7 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // 2-bit quantise (+EF)            replaces _int2_quant_fastpath (fastpath.py:486-580)
 // ---------------------------------------------------------------------------------------------------
 
+template <class E>
 __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C, int R, int flags) {
     const cfx_comp_item it = batch.it[blockIdx.z];
     const TileCoord t = tile_coord(N, C, R);
@@ -1149,7 +1150,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
         for (int j = 0; j < UNROLL; ++j) {
             const int rr = r + WAVES * j;
             if (rr < t.r1 && t.act) {
-                const h16x8 d = xv[j] - bv[j];
+                const h16x8 d = el_diff<E>(xv[j], bv[j]);
                 const h16x8 thr = ch8 * tk[j];                                   // fastpath.py:536
                 const h16x8 a = habs8(d);
                 unsigned code = 0;
@@ -1164,7 +1165,9 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
                     h16x8 o;
                     if (ef) {
                         const h16x8 recv = int2_recv((u16)code, thr);
-                        o = base ? (bv[j] + recv) : recv;
+                        // (fp16 written out: through el_state this kernel's fp16 form allocates one register more than it did)
+                        if constexpr (E::bf16) o = el_state<E>(base != nullptr, bv[j], recv);
+                        else o = base ? (bv[j] + recv) : recv;
                     } else {
                         o = xv[j];
                     }
@@ -1176,6 +1179,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
 }
 
 // 2-bit dequant + base add        replaces _int2_dequant_fastpath (fastpath.py:672-741)
+template <class E>
 __global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
     // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
     if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
@@ -1211,7 +1215,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int 
             if (rr < t.r1 && t.act) {
                 const h16x8 thr = ch8 * tk[j];
                 const h16x8 recv = int2_recv(cd[j], thr);
-                st8nt(out + (size_t)rr * C + t.c, base ? (bv[j] + recv) : recv);
+                st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bv[j], recv));
             }
         }
     }
@@ -1228,7 +1232,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int 
 // state was slower than three launches: its preload and the late D workgroups' burst landed on the reduction tail.  Two launches -
 // statistics + finalize alone, then quantise + gated reconstruction - measured 2.08 vs 2.04 ms per step for this form.)
 // ---------------------------------------------------------------------------------------------------
-template <int NW, int KR, int KL>
+template <int NW, int KR, int KL, class E = ElemF16>
 __device__ __forceinline__ void int2_dequant_gated_body(const cfx_decomp_item& it, int N, int C, int R, int tile_x, int tile_y,
                                                        unsigned* gate, unsigned expect, unsigned* err, long long timeout, u32x4* lds,
                                                        unsigned* xgate = nullptr, unsigned xexpect = 0, bool remote = false,
@@ -1307,7 +1311,7 @@ __device__ __forceinline__ void int2_dequant_gated_body(const cfx_decomp_item& i
             h16x8 bj = (h16x8)(h16)0;
             if (j < KR) bj = bv[j < KR ? j : 0];
             else if (base) bj = __builtin_bit_cast(h16x8, lds[(j - KR) * (NW * 64) + threadIdx.x]);
-            st8nt(out + (size_t)rr * C + t.c, base ? (bj + recv) : recv);
+            st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bj, recv));
         }
     }
 }
@@ -1332,7 +1336,7 @@ struct Int2LayerArgs {
     int remote;                            // group D's packets may sit in a peer GPU's memory
     P2PInline p2p;                         // own != NULL: workgroup 0 runs the peer-to-peer exchange and opens xgate itself
 };
-template <int US>
+template <int US, class E>
 __global__ __launch_bounds__(FUSED_NT, 4) void k_int2_compress_gated(BatchC batch, BatchD gated, Int2LayerArgs a) {
     // the statistics group: FUSED_NW rows + 4 (a parked row of x, of the state); the reconstruction group: GATE_LDS_ROWS of parked state + 1 of scales
     __shared__ u64 sm[(GATE_LDS_ROWS > FUSED_NW + 4 ? GATE_LDS_ROWS : FUSED_NW + 4) + 1][TILE_C];
@@ -1341,7 +1345,7 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_int2_compress_gated(BatchC batc
         const int per = a.CB * a.P;
         const int z = b / per, rem = b - z * per;
         const int by = rem / a.CB;
-        absmean_fused_body<false, US, true, true>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
+        absmean_fused_body<false, US, true, true, E>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
                                                   a.tick + z * TICK_WORDS, 4, 1, sm, 0, Probe(), a.gate1, a.expect1, a.flags, a.gate2, a.expect2, a.err, a.timeout,
                                                   tag_arena_of(a.tarena, a.tarena_stride, z, a.N, a.C, a.CB, a.P, a.tag));
         // (packets complete = the codes gate's last arriver has written the "open" words: XCD 0's)
@@ -1355,7 +1359,7 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_int2_compress_gated(BatchC batc
     const int sz = a.src[item];
     const TagArena ta = tag_arena_of(a.tarena, a.tarena_stride, sz >= 0 ? sz : 0, a.N, a.C, a.CB, a.P, a.tag);
     // (s16: behind the KL rows of state the workgroup parks in LDS)
-    int2_dequant_gated_body<FUSED_NW, GATE_KR2, GATE_KL>(gated.it[item], a.N, a.C, a.g_R, rem - ty * a.CB, ty, a.gate2, a.expect2, a.err, a.timeout,
+    int2_dequant_gated_body<FUSED_NW, GATE_KR2, GATE_KL, E>(gated.it[item], a.N, a.C, a.g_R, rem - ty * a.CB, ty, a.gate2, a.expect2, a.err, a.timeout,
                                                         (u32x4*)&sm[0][0], a.xgate, a.xexpect, a.remote != 0 && sz < 0, INT2_D_TAGGED && sz >= 0, ta, a.R,
                                                         (u16*)&sm[GATE_LDS_ROWS][0]);
 }
@@ -1367,6 +1371,12 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_int2_compress_gated(BatchC batc
 // The gated form can run as one launch when: 1-bit codec, in-launch finalize on, rows of sign bits 16-byte aligned (C % 128 == 0),
 // tiles of at most FUSED_NW * GATE_KR (1-bit) / FUSED_NW * (GATE_KR2 + GATE_KL) (2-bit) rows cover the tensor with few enough workgroups to matter.  Otherwise the same work runs as
 // compress + one reconstruction launch (identical results).
+// A launch of the kernel instantiated for the call's element type: `EL` names it inside the kernel expression.
+#define LAUNCH_EL(bf16, ...) do { \
+        if (bf16) { using EL = ElemBF16; LAUNCH(__VA_ARGS__); } \
+        else { using EL = ElemF16; LAUNCH(__VA_ARGS__); } \
+    } while (0)
+
 static bool gated_one_launch(cfx_ctx* ctx, int codec, int C, int CB) {
     return (codec == CFX_CODEC_BINARY || codec == CFX_CODEC_INT2) && ctx->fused && CB <= TICK_MAX_CB && C % 128 == 0 && !ctx->dev_probe && ctx->gated_on;
 }
@@ -1422,7 +1432,7 @@ int cfx_i_absmean_compress(CompressCall& cc) {
     BatchD rd = cc.rd, gd = cc.gd;
     u64* ws = cc.ws;
     const size_t wstride = cc.wstride;
-    const bool upd = cc.upd, capturing = cc.capturing;
+    const bool upd = cc.upd, capturing = cc.capturing, bf16 = cc.bf16;
     (void)param; (void)n_ride; (void)items; (void)gated; (void)rd; (void)ws; (void)wstride; (void)upd; (void)capturing; (void)xg; (void)gd;
     const bool fused = cc.fused;
     unsigned* tick = cc.tick;
@@ -1438,8 +1448,10 @@ int cfx_i_absmean_compress(CompressCall& cc) {
     if (one_launch && codec == CFX_CODEC_INT2) {
         // the 2-bit layer launch needs every statistics workgroup CO-RESIDENT (each waits at gate 1 for all the others' partial sums
         // while holding its tile in registers): only when they fit the CUs this stream may use, otherwise the multi-launch form
-        static int per_cu = 0;
-        if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_int2_compress_gated<4>, FUSED_NT, 0) != hipSuccess || per_cu < 1)) {
+        static int per_cu_el[2] = {0, 0};
+        int& per_cu = per_cu_el[bf16 ? 1 : 0];
+        if (!per_cu && ((bf16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_int2_compress_gated<4, ElemBF16>, FUSED_NT, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_int2_compress_gated<4, ElemF16>, FUSED_NT, 0)) != hipSuccess || per_cu < 1)) {
             (void)hipGetLastError();
             per_cu = 1;
         }
@@ -1458,8 +1470,10 @@ int cfx_i_absmean_compress(CompressCall& cc) {
         // n_g workgroups are all that is left of this launch; if they leave 32 workgroup slots of the stream's CUs free, at least 16 CUs
         // hold at most one of them - 320 free VGPRs per SIMD and 128 KB of LDS there, room for a workgroup of RCCL's kernel (256 threads x
         // 280 VGPRs, 20 KB) - and nothing of the launch is pending that could take those slots.  Otherwise: two launches.
-        static int per_cu = 0;
-        if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_absmean_compress<true, 4, true>, FUSED_NT, 0) != hipSuccess || per_cu < 1)) {
+        static int per_cu_el[2] = {0, 0};
+        int& per_cu = per_cu_el[bf16 ? 1 : 0];
+        if (!per_cu && ((bf16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_absmean_compress<true, 4, true, false, ElemBF16>, FUSED_NT, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_absmean_compress<true, 4, true, false, ElemF16>, FUSED_NT, 0)) != hipSuccess || per_cu < 1)) {
             (void)hipGetLastError();
             per_cu = 1;
         }
@@ -1508,7 +1522,7 @@ int cfx_i_absmean_compress(CompressCall& cc) {
             xg->f_gate = a.xgate; xg->f_expect = a.xexpect;
         }
         const dim3 g(a.n_st + a.n_g);
-        LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_int2_compress_gated<4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
+        LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_int2_compress_gated<4, EL>), g, dim3(FUSED_NT), 0, s, b, gd, a);
         return check_launch(ctx, "2-bit layer launch");
     }
     // 1-bit, one launch, CFX_FLAG_UPDATE_CACHE: the error-feedback update is the receiver's reconstruction of our own packet onto our
@@ -1567,30 +1581,30 @@ int cfx_i_absmean_compress(CompressCall& cc) {
         const dim3 g(a.n_st + a.n_g + CB * a.dq_rb * n_ride);
 #ifdef CFX_DEV_PROBES
         if (one_launch_1bit && ctx->dev_buf && R % 32 == 0) {          // (the instantiation whose reconstruction tiles drain before they stamp)
-            LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_absmean_compress<true, 4, true, true>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
+            LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_absmean_compress<true, 4, true, true, EL>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
         } else
 #endif
         if (one_launch_1bit) {
-            LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_absmean_compress<true, 4, true>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
+            LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_absmean_compress<true, 4, true, false, EL>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
         } else if (codec == CFX_CODEC_BINARY) {
-            if (R % 32 == 0) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_BITS, s, (k_absmean_compress<true, 4>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
-            else LAUNCH(ctx, KID_ABSMEAN_COMPRESS_BITS, s, (k_absmean_compress<true, 2>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
+            if (R % 32 == 0) LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS_BITS, s, (k_absmean_compress<true, 4, false, false, EL>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
+            else LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS_BITS, s, (k_absmean_compress<true, 2, false, false, EL>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
         } else {
-            if (R % 32 == 0) LAUNCH(ctx, KID_ABSMEAN_COMPRESS, s, (k_absmean_compress<false, 4>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
-            else LAUNCH(ctx, KID_ABSMEAN_COMPRESS, s, (k_absmean_compress<false, 2>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
+            if (R % 32 == 0) LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS, s, (k_absmean_compress<false, 4, false, false, EL>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
+            else LAUNCH_EL(bf16, ctx, KID_ABSMEAN_COMPRESS, s, (k_absmean_compress<false, 2, false, false, EL>), g, dim3(FUSED_NT), 0, s, b, rd, gd, a);
         }
     } else {
-        if (codec == CFX_CODEC_BINARY) LAUNCH(ctx, KID_ABSMEAN_STATS_BITS, s, k_absmean_stats<true>, grid, dim3(NTHR), 0, s, b, N, C, R, ws, wstride);
-        else LAUNCH(ctx, KID_ABSMEAN_STATS, s, k_absmean_stats<false>, grid, dim3(NTHR), 0, s, b, N, C, R, ws, wstride);
+        if (codec == CFX_CODEC_BINARY) LAUNCH_EL(bf16, ctx, KID_ABSMEAN_STATS_BITS, s, (k_absmean_stats<true, EL>), grid, dim3(NTHR), 0, s, b, N, C, R, ws, wstride);
+        else LAUNCH_EL(bf16, ctx, KID_ABSMEAN_STATS, s, (k_absmean_stats<false, EL>), grid, dim3(NTHR), 0, s, b, N, C, R, ws, wstride);
         LAUNCH(ctx, KID_ABSMEAN_FINALIZE, s, k_absmean_finalize, dim3(1 + (C + 255) / 256, batch), dim3(1024), 0, s, b, N, C, CB, P, per_byte,
                            codec == CFX_CODEC_INT2 ? 1 : 0, (const u64*)ws, wstride);
         if (n_ride) {
             const int Rr = auto_rows(ctx, N, C, n_ride, false);
-            LAUNCH(ctx, KID_BINARY_DEQUANT, s, k_binary_dequant<UNROLL>, dim3(CB, (N + Rr - 1) / Rr, n_ride), dim3(NTHR), 0, s, rd, N, C, Rr, (unsigned*)nullptr, 0u);
+            LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<UNROLL, EL>), dim3(CB, (N + Rr - 1) / Rr, n_ride), dim3(NTHR), 0, s, rd, N, C, Rr, (unsigned*)nullptr, 0u);
         }
     }
     if (codec == CFX_CODEC_INT2) {
-        LAUNCH(ctx, KID_INT2_QUANT, s, k_int2_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
+        LAUNCH_EL(bf16, ctx, KID_INT2_QUANT, s, (k_int2_quant<EL>), gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
     } else if (upd && !one_launch_1bit) {       // (one launch: the statistics workgroups did it from registers)
         if (flags & CFX_FLAG_NO_EF) {
             for (int i = 0; i < batch; ++i)
@@ -1603,27 +1617,27 @@ int cfx_i_absmean_compress(CompressCall& cc) {
             BatchD d;
             memset(&d, 0, sizeof(d));
             for (int i = 0; i < batch; ++i) { d.it[i].packet = items[i].packet; d.it[i].base = items[i].base; d.it[i].recon = items[i].new_base; }
-            LAUNCH(ctx, KID_BINARY_EF, s, k_binary_dequant<UNROLL>, gridq, dim3(NTHR), 0, s, d, N, C, Rq, (unsigned*)nullptr, 0u);
+            LAUNCH_EL(bf16, ctx, KID_BINARY_EF, s, (k_binary_dequant<UNROLL, EL>), gridq, dim3(NTHR), 0, s, d, N, C, Rq, (unsigned*)nullptr, 0u);
         }
     }
     if (n_gated && !(one_launch_1bit || (one_launch && codec == CFX_CODEC_INT2))) {
         const int Rg = auto_rows(ctx, N, C, n_gated, false);
-        if (codec == CFX_CODEC_BINARY) LAUNCH(ctx, KID_BINARY_DEQUANT, s, k_binary_dequant<UNROLL>, dim3(CB, (N + Rg - 1) / Rg, n_gated), dim3(NTHR), 0, s, gd, N, C, Rg, (unsigned*)nullptr, 0u);
-        else LAUNCH(ctx, KID_INT2_DEQUANT, s, k_int2_dequant, dim3(CB, (N + Rg - 1) / Rg, n_gated), dim3(NTHR), 0, s, gd, N, C, Rg, (unsigned*)nullptr, 0u);
+        if (codec == CFX_CODEC_BINARY) LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<UNROLL, EL>), dim3(CB, (N + Rg - 1) / Rg, n_gated), dim3(NTHR), 0, s, gd, N, C, Rg, (unsigned*)nullptr, 0u);
+        else LAUNCH_EL(bf16, ctx, KID_INT2_DEQUANT, s, (k_int2_dequant<EL>), dim3(CB, (N + Rg - 1) / Rg, n_gated), dim3(NTHR), 0, s, gd, N, C, Rg, (unsigned*)nullptr, 0u);
     }
     return check_launch(ctx, "compress launch");
 }
 
-int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val) {
+int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, bool bf16, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val) {
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, batch);
     if (codec == CFX_CODEC_BINARY) {
         if (stream_cu_count(ctx, stream) < 128) {
             // a CU-masked lane is bound by the bytes each CU keeps in flight: 4 rows per wave instead of 2
             const int R4 = WAVES * 4;
-            LAUNCH(ctx, KID_BINARY_DEQUANT, s, k_binary_dequant<4>, dim3(grid.x, (N + R4 - 1) / R4, batch), dim3(NTHR), 0, s, b, N, C, R4, pre, pre_val);
-        } else LAUNCH(ctx, KID_BINARY_DEQUANT, s, k_binary_dequant<UNROLL>, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
-    } else LAUNCH(ctx, KID_INT2_DEQUANT, s, k_int2_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+            LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<4, EL>), dim3(grid.x, (N + R4 - 1) / R4, batch), dim3(NTHR), 0, s, b, N, C, R4, pre, pre_val);
+        } else LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<UNROLL, EL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+    } else LAUNCH_EL(bf16, ctx, KID_INT2_DEQUANT, s, (k_int2_dequant<EL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
     return check_launch(ctx, "decompress launch");
 }
 
@@ -1632,6 +1646,7 @@ extern "C" {
 // The 2-bit quantise kernel ALONE, scales given: the packet tail already holds tok (N halves) and chan (C halves) - the Triton kernel
 // _int2_quant_fastpath (fastpath.py:486-580) as the reference launches it after its eager scale prologue.
 int cfx_int2_quantize(cfx_ctx* ctx, int N, int C, int flags, int batch, const cfx_comp_item* items, void* stream) {
+    const bool bf16 = (flags & CFX_FLAG_ELEM_BF16) != 0;      // (x, base, new_base bf16: this entry point has no codec argument to carry CFX_ELEM_BF16)
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "int2_quantize: null ctx/items");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "int2_quantize: batch out of range");
     if (!shape_ok(CFX_CODEC_INT2, N, C, 0)) return fail(ctx, CFX_ERR_SHAPE, "int2_quantize: bad shape");
@@ -1647,7 +1662,7 @@ int cfx_int2_quantize(cfx_ctx* ctx, int N, int C, int flags, int batch, const cf
     }
     hipStream_t s = (hipStream_t)stream;
     const int Rq = auto_rows(ctx, N, C, batch, true);
-    LAUNCH(ctx, KID_INT2_QUANT, s, k_int2_quant, dim3((C + TILE_C - 1) / TILE_C, (N + Rq - 1) / Rq, batch), dim3(NTHR), 0, s, b, N, C, Rq, flags);
+    LAUNCH_EL(bf16, ctx, KID_INT2_QUANT, s, (k_int2_quant<EL>), dim3((C + TILE_C - 1) / TILE_C, (N + Rq - 1) / Rq, batch), dim3(NTHR), 0, s, b, N, C, Rq, flags);
     return check_launch(ctx, "int2 quantise launch");
 }
 }  // extern "C"

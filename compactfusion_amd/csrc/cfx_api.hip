@@ -125,6 +125,8 @@ __global__ __launch_bounds__(256) void k_attn_merge(float* __restrict__ out, flo
 // host side: C-ABI
 // ---------------------------------------------------------------------------------------------------
 static bool shape_ok(int codec, int N, int C, int param) {
+    bool bf16;
+    codec = codec_id(codec, &bf16);                 // (the sizes and shape rules of a bf16 call are the fp16 codec's)
     if (N <= 0 || C <= 0 || (C % 8) != 0) return false;
     switch (codec) {
         case CFX_CODEC_BINARY: return ((size_t)N * (C / 8)) % 2 == 0;
@@ -365,7 +367,7 @@ int cfx_set_rows_per_tile(cfx_ctx* ctx, int rows) {
 size_t cfx_packet_bytes(int codec, int N, int C, int param) {
     if (!shape_ok(codec, N, C, param)) return 0;
     const size_t n = N, c = C;
-    switch (codec) {
+    switch (codec & 0xff) {
         case CFX_CODEC_BINARY: return n * c / 8 + 2 * (n + c);
         case CFX_CODEC_INT2: return n * c / 4 + 2 * (n + c);
         case CFX_CODEC_INT4: return n * c / 2 + 4 * c;
@@ -378,7 +380,7 @@ size_t cfx_packet_bytes(int codec, int N, int C, int param) {
 // per-tensor workspace in u64 words (worst case R = 16)
 static size_t ws_words(int codec, int N, int C) {
     const size_t CB = (C + TILE_C - 1) / TILE_C, P = (N + 15) / 16;
-    switch (codec) {
+    switch (codec & 0xff) {
         case CFX_CODEC_BINARY:
         case CFX_CODEC_INT2: return (size_t)N * CB + P * C + ((size_t)N * CB + P * C + 1) / 2;      // + the 32-bit partials of the fused path
         case CFX_CODEC_INT4:
@@ -413,8 +415,10 @@ static int stream_cu_count_impl(cfx_ctx* ctx, void* stream) {
 }
 
 // pre != NULL: the launch first publishes pre_val at *pre (exchange lane: "the reconstruction in front of this one is complete")
-int cfx_i_decompress_checked(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items, void* stream,
+int cfx_i_decompress_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int param, int batch, const cfx_decomp_item* items, void* stream,
                            unsigned* pre, unsigned pre_val) {
+    bool bf16 = false;
+    const int codec = codec_id(codec_arg, &bf16);
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "decompress: null ctx/items");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "decompress: batch out of range");
     if (!shape_ok(codec, N, C, param)) return fail(ctx, codec >= 1 && codec <= 5 ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
@@ -428,7 +432,7 @@ int cfx_i_decompress_checked(cfx_ctx* ctx, int codec, int N, int C, int param, i
     const int R = auto_rows(ctx, N, C, batch, false);
     switch (codec) {
         case CFX_CODEC_BINARY:
-        case CFX_CODEC_INT2: return cfx_i_absmean_decompress(ctx, codec, N, C, batch, b, R, stream, pre, pre_val);
+        case CFX_CODEC_INT2: return cfx_i_absmean_decompress(ctx, codec, bf16, N, C, batch, b, R, stream, pre, pre_val);
         case CFX_CODEC_INT4:
         case CFX_CODEC_INT8: return cfx_i_minmax_decompress(ctx, codec, N, C, batch, b, R, stream, pre, pre_val);
         default: return cfx_i_topk_decompress(ctx, N, C, param, batch, b, stream, pre, pre_val);
@@ -495,9 +499,11 @@ void cfx_i_fill_p2p(cfx_ctx* ctx, CfxXGate* xg, P2PInline& p) {
     xg->inline_done = 1;
 }
 
-static int compress_impl(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
+static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
                          int n_ride, const cfx_decomp_item* ride, int n_gated, const cfx_decomp_item* gated,
                          void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg = nullptr) {
+    bool bf16 = false;
+    const int codec = codec_id(codec_arg, &bf16);      // (0: no such codec - the shape check below says so)
     if (xg) { xg->taken = 0; xg->inline_done = 0; xg->p_gate = xg->f_gate = nullptr; xg->p_expect = xg->f_expect = 0; xg->p_count = 1; }
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "compress: null ctx/items");
     if (n_gated < 0 || n_gated > CFX_MAX_BATCH || (n_gated && !gated)) return fail(ctx, CFX_ERR_BATCH, "compress: gated batch out of range");
@@ -552,7 +558,7 @@ static int compress_impl(cfx_ctx* ctx, int codec, int N, int C, int param, int f
     CompressCall cc;
     cc.ctx = ctx; cc.codec = codec; cc.N = N; cc.C = C; cc.param = param; cc.flags = flags; cc.batch = batch; cc.items = items;
     cc.n_ride = n_ride; cc.n_gated = n_gated; cc.gated = gated; cc.stream = stream; cc.xg = xg; cc.b = b; cc.rd = rd; cc.gd = gd;
-    cc.ws = ws; cc.wstride = wstride; cc.CB = CB; cc.upd = upd; cc.capturing = capturing;
+    cc.ws = ws; cc.wstride = wstride; cc.CB = CB; cc.upd = upd; cc.capturing = capturing; cc.bf16 = bf16;
     cc.fused = false; cc.tick = nullptr; cc.slot = 0; cc.stream_cus = 0; cc.R = cc.P = 0;
     if (codec == CFX_CODEC_TOPK) return cfx_i_topk_compress(cc);
 
@@ -649,7 +655,7 @@ bool cfx_i_shape_ok(int codec, int N, int C, int param) { return shape_ok(codec,
 // The 2-bit layer launch takes the external gate too (k_int2_compress_gated's group D).  With the exchange as a one-wave kernel on an exchange
 // stream it measured 2.40-2.46 ms per FLUX step against 2.03 for three launches in stream order - a resident polling kernel on another queue
 // alone costs that launch 4 us per layer (tools/xgate_probe.py, kind gated+poller) -; with the exchange INSIDE the launch (P2PInline) 2.11.
-bool cfx_i_has_xlayer_form(int codec) { return codec >= CFX_CODEC_BINARY && codec <= CFX_CODEC_TOPK; }
+bool cfx_i_has_xlayer_form(int codec) { return (codec & 0xff) >= CFX_CODEC_BINARY && (codec & 0xff) <= CFX_CODEC_TOPK; }
 unsigned* cfx_i_ticket_block(cfx_ctx* ctx, void* stream) {
     if (!ctx->tick && cfx_prepare(ctx) != CFX_OK) return nullptr;
     return ctx->tick + (size_t)ticket_slot(ctx, stream) * CFX_MAX_BATCH * TICK_WORDS;

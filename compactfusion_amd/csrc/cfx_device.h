@@ -14,6 +14,10 @@ typedef h16 h16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 typedef u16 u16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned long long u64;
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef h16 h16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 #define TILE_C 512      // channels per wave-row = 64 lanes x 8 halves
 #define WAVES 4         // waves per workgroup
@@ -100,7 +104,6 @@ __device__ __forceinline__ unsigned char ld_sys(const unsigned char* p) { return
 // 16-byte write-through store (an agent-scope atomic store lowers to `sc1` only up to 8 bytes).  hipcc does not count an asm
 // store: the publishing wave drains it with its own `s_waitcnt vmcnt(0)`; the trailing s_nop keeps the data registers alive
 // until the store has read them (cdna_hip_programming.md 5.7).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st16_wt(void* p, u32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
@@ -178,6 +181,52 @@ __device__ __forceinline__ h16x8 habs8(h16x8 v) {
     u16x8 b = __builtin_bit_cast(u16x8, v);
     b &= (u16)0x7fff;
     return __builtin_bit_cast(h16x8, b);
+}
+
+// Element type of the activations and states a kernel loads and stores (include/cfx.h, "Conventions"): fp16, or bf16 AROUND the fp16
+// residual domain -  d = fp16(fp32(x) - fp32(base))  going in,  state = bf16(fp32(base) + fp32(recv))  coming out, one rounding each;
+// everything between d and recv (sign bits, codes, exact sums, scales, packet bytes) is the fp16 path's.  A lane's 8 elements travel as
+// an h16x8 either way - for bf16 the raw 16-bit words, converted where they are used - so registers, parked tiles, loads and stores do
+// not change; the fp16 case of every function below is the expression it replaced.
+struct ElemF16 { static constexpr bool bf16 = false; };
+struct ElemBF16 { static constexpr bool bf16 = true; };
+// bf16 -> fp32 is a shift (the low element of a word) or a mask (the high one); fp32 -> bf16 / fp16 are gfx950's packed converts
+// (v_cvt_pk_bf16_f32, v_cvt_pk_f16_f32: round to nearest even)
+__device__ __forceinline__ f32x2 bf2_f32(unsigned w) {
+    return f32x2{__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
+}
+__device__ __forceinline__ unsigned f32_bf2(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
+// d = x - base in the residual domain
+template <class E>
+__device__ __forceinline__ h16x8 el_diff(h16x8 x, h16x8 b) {
+    if constexpr (!E::bf16) return x - b;
+    else {
+        const u32x4 xw = __builtin_bit_cast(u32x4, x), bw = __builtin_bit_cast(u32x4, b);
+        h16x8 d;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const h16x2 h = __builtin_convertvector(bf2_f32(xw[w]) - bf2_f32(bw[w]), h16x2);
+            d[2 * w] = h[0];
+            d[2 * w + 1] = h[1];
+        }
+        return d;
+    }
+}
+// state = base + recv (no base: recv)
+template <class E>
+__device__ __forceinline__ h16x8 el_state(bool has_base, h16x8 b, h16x8 recv) {
+    if constexpr (!E::bf16) return has_base ? (b + recv) : recv;
+    else {
+        // (the sum of +0 and recv would lose the sign of a zero: no base is its own case, as in the fp16 expression)
+        const u32x4 bw = __builtin_bit_cast(u32x4, b);
+        u32x4 o;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const f32x2 r = {(float)recv[2 * w], (float)recv[2 * w + 1]};
+            o[w] = f32_bf2(has_base ? bf2_f32(bw[w]) + r : r);
+        }
+        return __builtin_bit_cast(h16x8, o);
+    }
 }
 
 // 2-bit codes -> received values (levels +-0.5 thr, +-2 thr)

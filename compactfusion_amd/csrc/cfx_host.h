@@ -18,6 +18,7 @@ struct CompressCall {
     u64* ws;
     size_t wstride;
     int CB;
+    bool bf16;                       // the call's tensors (x, base, new_base, recon) are bf16: CFX_ELEM_BF16 on the codec argument
     bool upd, capturing;             // capturing: the stream is under hipGraph capture - no one-launch layer form (include/cfx.h)
     // the tile geometry of the abs-mean and min/max families' compress launches (compress_impl, before the dispatch)
     bool fused;
@@ -30,7 +31,7 @@ CFX_HIDDEN int cfx_i_topk_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_absmean_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_minmax_compress(CompressCall& cc);
 // reconstruction launches of a validated batch (decompress_impl's dispatch); `pre` / `pre_val`: an optional flag word the kernel waits for
-CFX_HIDDEN int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
+CFX_HIDDEN int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, bool bf16, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_minmax_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_topk_decompress(cfx_ctx* ctx, int N, int C, int param, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
 // cfx_api.hip

@@ -169,6 +169,16 @@ static inline int check_launch(cfx_ctx* ctx, const char* what) {
 
 #define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
+// A `codec` argument of the ABI -> the codec id and the element type of the call's tensors (CFX_ELEM_BF16, include/cfx.h).  0 - no codec -
+// for any other high bit and for the bf16 bit on a codec that has no bf16 form.
+static inline int codec_id(int codec_arg, bool* bf16) {
+    const int id = codec_arg & 0xff;
+    *bf16 = (codec_arg & CFX_ELEM_BF16) != 0;
+    if (codec_arg < 0 || (codec_arg & ~(0xff | CFX_ELEM_BF16))) return 0;
+    if (*bf16 && id != CFX_CODEC_BINARY && id != CFX_CODEC_INT2) return 0;
+    return id;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Plan / communicator internals, shared by cfx_absmean.hip (the fused pipeline launch) and cfx_plan.hip (everything else)
 // ---------------------------------------------------------------------------------------------------

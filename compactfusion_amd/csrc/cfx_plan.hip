@@ -230,7 +230,10 @@ int cfx_plan_add_compress_ex(cfx_plan* p, int codec, int N, int C, int param, in
     if (!p || !items) return CFX_ERR_NULL;
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(p->ctx, CFX_ERR_BATCH, "plan: batch out of range");
     if (n_ride < 0 || n_ride > CFX_MAX_BATCH || (n_ride && !ride)) return fail(p->ctx, CFX_ERR_BATCH, "plan: ride-along batch out of range");
-    if (n_ride && codec != CFX_CODEC_BINARY) return fail(p->ctx, CFX_ERR_CODEC, "plan: ride-along reconstruction items need the 1-bit codec");
+    bool bf16 = false;
+    const int id = codec_id(codec, &bf16);
+    if (n_ride && id != CFX_CODEC_BINARY) return fail(p->ctx, CFX_ERR_CODEC, "plan: ride-along reconstruction items need the 1-bit codec");
+    if (!id && codec >= 0x100) return fail(p->ctx, CFX_ERR_CODEC, "plan: no such codec / element type");
     if (!shape_ok(codec, N, C, param)) return fail(p->ctx, CFX_ERR_SHAPE, "plan: bad codec/shape");
     PlanOp* o = plan_push(p);
     memset(o, 0, sizeof(*o));
@@ -250,6 +253,8 @@ int cfx_plan_add_compress(cfx_plan* p, int codec, int N, int C, int param, int f
 int cfx_plan_add_decompress(cfx_plan* p, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items) {
     if (!p || !items) return CFX_ERR_NULL;
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(p->ctx, CFX_ERR_BATCH, "plan: batch out of range");
+    bool bf16 = false;
+    if (!codec_id(codec, &bf16) && codec >= 0x100) return fail(p->ctx, CFX_ERR_CODEC, "plan: no such codec / element type");
     if (!shape_ok(codec, N, C, param)) return fail(p->ctx, CFX_ERR_SHAPE, "plan: bad codec/shape");
     PlanOp* o = plan_push(p);
     memset(o, 0, sizeof(*o));
@@ -307,7 +312,8 @@ static int add_exchange_layer(cfx_plan* p, int codec, int N, int C, int param, i
                               void* workspace, size_t workspace_bytes, bool need_side) {
     if (!p) return CFX_ERR_NULL;
     if (n_recon < 1 || n_recon > CFX_MAX_BATCH || !recon) return fail(p->ctx, CFX_ERR_BATCH, "plan: exchange layer needs 1..CFX_MAX_BATCH reconstruction items");
-    if (codec < CFX_CODEC_BINARY || codec > CFX_CODEC_TOPK) return fail(p->ctx, CFX_ERR_CODEC, "plan: exchange layer: unknown codec");
+    bool bf16 = false;
+    if (!codec_id(codec, &bf16) || (codec & 0xff) > CFX_CODEC_TOPK) return fail(p->ctx, CFX_ERR_CODEC, "plan: exchange layer: unknown codec");
     if (comm && (!send || !recv)) return fail(p->ctx, CFX_ERR_NULL, "plan: exchange layer: null send/recv");
     if (!p->side && need_side) {
         // the flag kernels poll: they need a hardware queue of their own (cfx.h, exchange lane) - a CU-masked stream has one

@@ -10,6 +10,11 @@ tests/test_gpu_quality.py (G12) and tests/test_gpu_stack.py (G13).  On a machine
         --preset binary --prompt "a photo of a cat" --out out/
 
 Presets follow the reference's examples/configs.py:39-98 (1 WARMUP step, residual 1 + error feedback).
+
+The pipeline is loaded with torch_dtype=torch.bfloat16, as the reference's examples load FLUX: K and V reach compact_fwd as bf16, and bf16
+is what the exchange runs - bf16 states around the fp16 residual codec and wire of the `binary` / `int2` presets ("bf16
+activations"), no cast to fp16 around the layers.  The other presets (int4 / int8 / top-k / low-rank) take fp16 activations only and raise
+NotImplementedError on bf16 K,V.
 """
 import argparse
 import os

@@ -19,7 +19,8 @@
  *   cfx_packet_bytes       replaces  the size arithmetic of  xfuser/compact/main.py:285-293, slowpath.py:111-135
  *
  * Conventions
- *   - All tensor pointers are DEVICE pointers to contiguous row-major (N, C) fp16 ("half") data.
+ *   - All tensor pointers are DEVICE pointers to contiguous row-major (N, C) fp16 ("half") data - or, for the 1-bit and 2-bit
+ *     codecs, bf16 data: see "bf16 activations" below.
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls are asynchronous.
  *   - No torch types, no exceptions: every call returns CFX_OK (0) or a negative error code and
  *     records a message retrievable with cfx_last_error_string().
@@ -34,6 +35,25 @@
  *   TOPK    [ val N*C/m fp16 | idx N*C/(2m) B : (i1<<4)|i2 per 2m-block of the flat (-1,1024) view ]           slowpath.py:76-79
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
  *   and N odd, int4 with C % 16 == 8 and N/2 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
+ *
+ * bf16 activations (CFX_CODEC_BINARY and CFX_CODEC_INT2 only)
+ *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,
+ *   cfx_compress[_batch[_ex|_gated]], cfx_decompress[_batch], cfx_plan_add_compress[_ex|_gated], cfx_plan_add_decompress,
+ *   cfx_plan_add_exchange_layer[_p2p], and through them cfx_plan_copy_op) says that ALL tensor operands of the call - x, base, new_base,
+ *   recon, of the compress, ride-along and gated items alike - are bf16.  cfx_int2_quantize, which has no codec argument, takes
+ *   CFX_FLAG_ELEM_BF16 in `flags`.  The residual domain and the wire stay fp16:
+ *       d        = fp16_rne( fp32(x) - fp32(base) )          one fp32 subtraction, one rounding to fp16; base NULL: d = fp16_rne(fp32(x))
+ *       d -> recv  exactly the fp16 path: sign bits / 2-bit codes, exact sums in units of 2^-24, fp16 scales, packet bytes;
+ *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels, in fp16
+ *       new_base = recon = bf16_rne( fp32(base) + fp32(recv) )     base NULL: bf16_rne(fp32(recv))
+ *       CFX_FLAG_NO_EF: new_base = x, copied verbatim as bf16 bits
+ *   Packet layout, cfx_packet_bytes and cfx_workspace_bytes are those of the fp16 codec: a bf16 sender's packet is a valid fp16-path
+ *   packet (a receiver may reconstruct it onto an fp16 state with the plain codec id, and the other way round).  Domain as for the
+ *   fp16 path: finite inputs with |x - base| < 65504; outside it the result is unspecified (see "Non-finite input").
+ *   The bit on codecs 3 - 5, and any other bit above the codec id, is CFX_ERR_CODEC; the sizes of such a codec argument are 0.
+ *   Every form the fp16 path has exists for bf16 (stand-alone, in-launch finalize, ride-along, one-launch layer forms, the peer-to-peer
+ *   exchange inside the launch), with the documented fall-backs; cfx_plan_run_pipelined and the rank-K 1-bit codec are fp16 only (a
+ *   pipelined replay of bf16 ops runs as cfx_plan_run).
  *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
  *   INT4 / INT8: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
@@ -78,16 +98,19 @@ enum cfx_codec {
     CFX_CODEC_INT8 = 4,      /* per-channel affine int8, zero point int16 */
     CFX_CODEC_TOPK = 5       /* COMPACT_COMPRESS_TYPE.SPARSE, param = m in {1,2,4,8,16} */
 };
+/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit and 2-bit codecs; "bf16 activations" above) */
+#define CFX_ELEM_BF16 0x100
 
 enum cfx_flags {
     CFX_FLAG_UPDATE_CACHE = 1, /* write new_base (compact_compress(update_cache=True)) */
-    CFX_FLAG_NO_EF = 2         /* error feedback off: new_base = x (main.py:233 `else x`) */
+    CFX_FLAG_NO_EF = 2,        /* error feedback off: new_base = x (main.py:233 `else x`) */
+    CFX_FLAG_ELEM_BF16 = 0x100 /* cfx_int2_quantize only (it has no codec argument): x, base, new_base are bf16 */
 };
 
 /* One tensor of a compress batch.  base may be NULL (compress_residual == 0: the codec sees x itself);
  * new_base may alias base (in-place error-feedback update) and is ignored unless CFX_FLAG_UPDATE_CACHE. */
 typedef struct cfx_comp_item {
-    const void* x;        /* (N,C) fp16, 16-byte aligned */
+    const void* x;        /* (N,C) fp16 (bf16 with CFX_ELEM_BF16: all three tensors), 16-byte aligned */
     const void* base;     /* (N,C) fp16, 16-byte aligned, or NULL */
     void*       new_base; /* (N,C) fp16, 16-byte aligned, or NULL */
     void*       packet;   /* cfx_packet_bytes() bytes, 16-byte aligned */
@@ -220,7 +243,7 @@ int cfx_decompress(cfx_ctx* ctx, int codec, const void* packet, const void* base
                    int N, int C, int param, void* stream);
 
 /* The 2-bit quantise kernel alone, SCALES GIVEN: each item's packet tail already holds tok (N fp16, after the N*C/4 code bytes) and chan
- * (C fp16); codes (+ error-feedback state with CFX_FLAG_UPDATE_CACHE) are written.  Replaces the Triton kernel _int2_quant_fastpath
+ * (C fp16); codes (+ error-feedback state with CFX_FLAG_UPDATE_CACHE) are written (CFX_FLAG_ELEM_BF16: x, base, new_base bf16).  Replaces the Triton kernel _int2_quant_fastpath
  * (xfuser/compact/fastpath.py:486-580) as the reference launches it behind its eager scale prologue (:614-625) - what a parity test
  * needs to compare codes bit for bit given the reference's own scale vectors. */
 int cfx_int2_quantize(cfx_ctx* ctx, int N, int C, int flags, int batch, const cfx_comp_item* items, void* stream);

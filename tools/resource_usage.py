@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-_FIELDS = (("name", r"Function Name: (\S+)"), ("sgpr", r" SGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("agpr", r" AGPRs: (\d+)"),
+_FIELDS = (("name", r"Function Name: (\S+)"), ("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("agpr", r" AGPRs: (\d+)"),
            ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"),
            ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
 
