@@ -20,6 +20,8 @@ FLAG_UPDATE_CACHE = 1
 FLAG_NO_EF = 2
 FLAG_ELEM_BF16 = 0x100   # cfx_int2_quantize only
 ELEM_BF16 = 0x100        # CFX_ELEM_BF16: or-ed into a `codec` argument - the call's tensors are bf16 (1-bit / 2-bit codecs)
+MERGE_BSHD = 1           # cfx_attn_merge_ex `flags` (with ELEM_BF16: block_out / final_out are bf16)
+MERGE_FIRST = 2
 
 
 class CompItem(ctypes.Structure):
@@ -149,6 +151,7 @@ SYMBOLS = [
     ("cfx_set_gate_timeout_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("cfx_attn_merge_wait", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
+    ("cfx_attn_merge_ex", ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
 ]
 
 # include/cfx_dev.h: exported by the DEVELOPER library only (libcfx_dev.so, -DCFX_DEV_PROBES).  Bound when - and only when - that library

@@ -42,11 +42,11 @@ def block_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p
 def update_out_and_lse(out: Optional[torch.Tensor], lse: Optional[torch.Tensor], block_out: torch.Tensor,
                        block_lse: torch.Tensor, wait=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Merge one attention block into the running (out fp32 (B,S,H,D), lse fp32 (B,S,H,1)).  On the GPU this is ONE native
-    launch (`cfx_attn_merge`) that reads the SDPA kernel's own (B,H,S,D) / (B,H,S) outputs and updates out / lse in place;
-    elsewhere (CPU tests of the host logic) the same formula in eager torch.
+    launch (`cfx_attn_merge_ex`; fp16 or bf16 blocks) that reads the SDPA kernel's own (B,H,S,D) / (B,H,S) outputs and updates
+    out / lse in place; elsewhere (CPU tests of the host logic) the same formula in eager torch.
     `wait` = (flag device address, epoch): the exchange lane's "next peer reconstructed" flag - the merge launch also waits for
-    it (`cfx_attn_merge_wait`), so the attention block that follows finds the peer's K,V complete without a stream event."""
-    if block_out.is_cuda and block_out.dtype == torch.float16 and block_lse.dtype == torch.float32 and block_out.shape[-1] % 8 == 0 \
+    it, so the attention block that follows finds the peer's K,V complete without a stream event."""
+    if block_out.is_cuda and block_out.dtype in (torch.float16, torch.bfloat16) and block_lse.dtype == torch.float32 and block_out.shape[-1] % 8 == 0 \
             and block_out.shape[-1] <= 512 and (out is None or (out.is_contiguous() and lse.is_contiguous() and out.dtype == torch.float32)):
         if block_lse.is_contiguous() and block_out.data_ptr() % 16 == 0:
             if block_out.is_contiguous():                  # the fused SDPA output, (B,S,H,D) contiguous underneath
@@ -89,11 +89,12 @@ def _merge_native(out, lse, bo, bl, bshd, wait=None):
         out = torch.empty((B, S, H, D), dtype=torch.float32, device=bo.device)
         lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=bo.device)
     if _merge_fn is None:
-        _merge_fn = _lib.load().cfx_attn_merge_wait
+        _merge_fn = _lib.load().cfx_attn_merge_ex
     ctx = codecs.context(dev)
-    rc = _merge_fn(ctx, out.data_ptr(), lse.data_ptr(), bo.data_ptr(), bl.data_ptr(), B, S, H, D, bshd, 1 if first else 0,
-                   wait[0] if wait is not None else None, wait[1] if wait is not None else 0,
+    flags = (_lib.MERGE_BSHD if bshd else 0) | (_lib.MERGE_FIRST if first else 0) | (_lib.ELEM_BF16 if bo.dtype == torch.bfloat16 else 0)
+    rc = _merge_fn(ctx, out.data_ptr(), lse.data_ptr(), bo.data_ptr(), bl.data_ptr(), B, S, H, D, flags,
+                   wait[0] if wait is not None else None, wait[1] if wait is not None else 0, None,
                    torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        codecs._check(ctx, rc, "cfx_attn_merge")
+        codecs._check(ctx, rc, "cfx_attn_merge_ex")
     return out, lse

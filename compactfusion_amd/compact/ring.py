@@ -292,15 +292,17 @@ class _SteadyLayer:
             return self._fast
         self._fast = False
         try:
-            if q.dtype == torch.float16 and q.shape[-1] % 8 == 0 and q.shape[-1] <= 512 and q.dim() == 4:
+            if q.dtype in (torch.float16, torch.bfloat16) and q.shape[-1] % 8 == 0 and q.shape[-1] <= 512 and q.dim() == 4:
                 from .. import _lib, codecs
                 sdpa = torch.ops.aten._scaled_dot_product_flash_attention
                 qt = q.transpose(1, 2)
                 r = sdpa(qt, qt, qt, 0.0, False, False, scale=1.0)
-                if (r[0].dtype == torch.float16 and r[0].transpose(1, 2).is_contiguous() and r[1].dtype == torch.float32 and r[1].is_contiguous()
+                if (r[0].dtype == q.dtype and r[0].transpose(1, 2).is_contiguous() and r[1].dtype == torch.float32 and r[1].is_contiguous()
                         and r[0].data_ptr() % 16 == 0):
                     dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
-                    self._sdpa, self._merge, self._ctx = sdpa, _lib.load().cfx_attn_merge_wait, codecs.context(dev)
+                    self._sdpa, self._merge, self._ctx = sdpa, _lib.load().cfx_attn_merge_ex, codecs.context(dev)
+                    self._mflags = _lib.MERGE_BSHD | (_lib.ELEM_BF16 if q.dtype == torch.bfloat16 else 0)
+                    self._mfirst = _lib.MERGE_FIRST
                     self._peer_t = [(s, kk.transpose(1, 2), vv.transpose(1, 2)) for s, kk, vv in self._peers]
                     self._fast = True
         except (RuntimeError, NotImplementedError):
@@ -347,17 +349,19 @@ class _SteadyLayer:
         """The layer's attention blocks in ring order - own K,V, then peer s = 1 .. W-1 - merged into one running out / lse.  The lane
         forms pass `issue` and `flag`: after block s, issue(s, lean) issues the chain launches that belong behind it, and the merge of
         block s < W-1 also waits, inside its launch, until flag(s + 1) - peer s+1 reconstructed - has reached `epoch`.  lean
-        (`_fast_ok`): the step is host-bound long before it is GPU-bound (8 attention + 8 merge calls per layer), so the fused SDPA op
-        and the merge are called directly, on cached transposed views of the peers' states; otherwise block_attention +
-        update_out_and_lse."""
+        (`_fast_ok`; fp16 and bf16): the step is host-bound long before it is GPU-bound (8 attention + 8 merge calls per layer), so the
+        fused SDPA op and the merge (`cfx_attn_merge_ex`) are called directly, on cached transposed views of the peers' states, and the
+        merge launch of the last block writes the result in q.dtype itself - no cast launch behind it; otherwise block_attention +
+        update_out_and_lse and the cast."""
         last = self.world - 1
         if self._fast_ok(q):
-            sdpa, merge, ctx = self._sdpa, self._merge, self._ctx
+            sdpa, merge, ctx, mflags = self._sdpa, self._merge, self._ctx, self._mflags
             B, S, H, D = q.shape
             qt = q.transpose(1, 2)
-            out = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+            acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device) if last else None     # the running fp32 out
+            out = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
             lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=q.device)
-            op, lp = out.data_ptr(), lse.data_ptr()
+            ap, op, lp = acc.data_ptr() if last else None, out.data_ptr(), lse.data_ptr()
             keep = []                                       # the SDPA results, held until their merges are enqueued
             for s, kt, vt in [(0, k.transpose(1, 2), v.transpose(1, 2))] + self._peer_t:
                 res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
@@ -367,19 +371,20 @@ class _SteadyLayer:
                     issue(s, True)
                     if s < last:
                         wait = flag(s + 1)
-                if merge(ctx, op, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, 1, s == 0, wait, epoch, sh) != 0:
+                if merge(ctx, ap, lp, res[0].data_ptr(), res[1].data_ptr(), B, S, H, D, mflags if s else mflags | self._mfirst, wait, epoch,
+                         op if s == last else None, sh) != 0:
                     from .. import _lib
-                    raise RuntimeError("cfx_attn_merge_wait failed: " + (_lib.load().cfx_last_error_string(ctx) or b"").decode())
-        else:
-            out = lse = None
-            for s, kk, vv in [(0, k, v)] + self._peers:
-                bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
-                wait = None
-                if issue is not None:
-                    issue(s, False)
-                    if s < last:
-                        wait = (flag(s + 1), epoch)
-                out, lse = update_out_and_lse(out, lse, bo, bl, wait)
+                    raise RuntimeError("cfx_attn_merge_ex failed: " + (_lib.load().cfx_last_error_string(ctx) or b"").decode())
+            return out, lse.squeeze(dim=-1).transpose(1, 2), None
+        out = lse = None
+        for s, kk, vv in [(0, k, v)] + self._peers:
+            bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
+            wait = None
+            if issue is not None:
+                issue(s, False)
+                if s < last:
+                    wait = (flag(s + 1), epoch)
+            out, lse = update_out_and_lse(out, lse, bo, bl, wait)
         return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
 
 

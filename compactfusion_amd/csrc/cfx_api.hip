@@ -70,6 +70,9 @@ __global__ __launch_bounds__(256) void k_residual2_update(const h16* base, const
 // first != 0: out = block_out, lse = block_lse.  One thread = 8 consecutive d of one (b, s, h); the D/8 threads of a row all
 // read lse[row] and one of them rewrites it in place, so a row's threads must sit in ONE wave (its load instruction then
 // precedes its store instruction for every lane): a row takes G = the power of two >= D/8 lanes (G <= 64), lanes d8 >= D/8 idle.
+// attn_merge_ex_body below is this body's twin (element type and final cast as template arguments; this one keeps its shape because
+// k_attn_merge's name and resources are pinned): an edit to the arithmetic of one belongs in the other too - the GPU tests hold the
+// two to the same bits (tests/test_gpu_attn_merge_bf16.py).
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void attn_merge_body(float* __restrict__ out, float* __restrict__ lse, const h16* __restrict__ bo,
                                                 const float* __restrict__ bl, int B, int S, int H, int D, int first,
@@ -117,6 +120,68 @@ __global__ __launch_bounds__(256) void k_attn_merge(float* __restrict__ out, flo
                                                     size_t bo_sb, size_t bo_ss, size_t bo_sh, int lg,
                                                     const unsigned* wflag, unsigned wval, unsigned* err, long long timeout) {
     attn_merge_body(out, lse, bo, bl, B, S, H, D, first, bo_sb, bo_ss, bo_sh, lg);
+    if (wflag && blockIdx.x == 0 && threadIdx.x == 0) flag_spin(wflag, wval, err, timeout);
+}
+
+// cfx_attn_merge_ex: the same merge with the block's element type a template argument (E: block_out fp16 or bf16 - only the load
+// differs, both widen to fp32 exactly) and, FINAL, the layer's last block: the merged row is not stored back as fp32 but rounded to
+// the element type (nearest even) into `fin`, a contiguous [B][S][H][D] tensor of its own, 16 bytes a thread - `out` is only read
+// (first && FINAL, a single block: not even that, fin takes the block's bits).  The arithmetic is attn_merge_body's, expression for
+// expression (the translation unit is compiled without fp contraction, so every instantiation rounds where that one does): what
+// FINAL rounds is the fp32 value the non-final form stores.
+template <class E, bool FINAL>
+__device__ __forceinline__ void attn_merge_ex_body(float* __restrict__ out, float* __restrict__ lse, const u16* __restrict__ bo,
+                                                   const float* __restrict__ bl, u16* __restrict__ fin, int B, int S, int H, int D, int first,
+                                                   size_t bo_sb, size_t bo_ss, size_t bo_sh, int lg) {
+    const int D8 = D >> 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t rows = (size_t)B * S * H;
+    const int d8 = (int)(i & ((1u << lg) - 1));
+    size_t r = i >> lg;
+    if (r >= rows || d8 >= D8) return;
+    const int h = (int)(r % H); r /= H;
+    const int s_ = (int)(r % S);
+    const int b = (int)(r / S);
+    const size_t o_idx = (((size_t)b * S + s_) * H + h) * D + (size_t)d8 * 8;
+    const size_t l_idx = ((size_t)b * S + s_) * H + h;
+    const size_t bo_idx = (size_t)b * bo_sb + (size_t)s_ * bo_ss + (size_t)h * bo_sh + (size_t)d8 * 8;
+    const float lb = bl[((size_t)b * H + h) * S + s_];
+    const h16x8 obw = ld8nt(reinterpret_cast<const h16*>(bo) + bo_idx);      // (the 16-bit words as they are: E says what they hold)
+    float ob[8];
+    el_widen8<E>(obw, ob);
+    float4* op = reinterpret_cast<float4*>(out + o_idx);
+    if (first) {
+        if constexpr (FINAL) st8(reinterpret_cast<h16*>(fin) + o_idx, obw);            // (fp32 of an element rounds back to the element's own bits)
+        else {
+            op[0] = make_float4(ob[0], ob[1], ob[2], ob[3]);
+            op[1] = make_float4(ob[4], ob[5], ob[6], ob[7]);
+        }
+        if (d8 == 0) lse[l_idx] = lb;
+        return;
+    }
+    // (the row's lse: read by every lane of its group before lane d8 == 0 of the same wave rewrites it, as in attn_merge_body)
+    const float l = __hip_atomic_load(lse + l_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const float x = lb - l;
+    const float sg = 1.0f / (1.0f + __expf(-x));                                    // sigmoid(lse_b - lse)
+    float4 a = op[0], c = op[1];
+    a.x -= sg * (a.x - ob[0]); a.y -= sg * (a.y - ob[1]); a.z -= sg * (a.z - ob[2]); a.w -= sg * (a.w - ob[3]);
+    c.x -= sg * (c.x - ob[4]); c.y -= sg * (c.y - ob[5]); c.z -= sg * (c.z - ob[6]); c.w -= sg * (c.w - ob[7]);
+    if constexpr (FINAL) {
+        const float m[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+        st8(reinterpret_cast<h16*>(fin) + o_idx, el_round8<E>(m));
+    } else {
+        op[0] = a; op[1] = c;
+    }
+    if (d8 == 0) lse[l_idx] = l + (fmaxf(x, 0.0f) + log1pf(__expf(-fabsf(x))));
+}
+
+template <class E, bool FINAL>
+__global__ __launch_bounds__(256) void k_attn_merge_ex(float* __restrict__ out, float* __restrict__ lse, const u16* __restrict__ bo,
+                                                       const float* __restrict__ bl, u16* __restrict__ fin, int B, int S, int H, int D,
+                                                       int first, size_t bo_sb, size_t bo_ss, size_t bo_sh, int lg,
+                                                       const unsigned* wflag, unsigned wval, unsigned* err, long long timeout) {
+    attn_merge_ex_body<E, FINAL>(out, lse, bo, bl, fin, B, S, H, D, first, bo_sb, bo_ss, bo_sh, lg);
     if (wflag && blockIdx.x == 0 && threadIdx.x == 0) flag_spin(wflag, wval, err, timeout);
 }
 
@@ -719,6 +784,34 @@ int cfx_attn_merge_wait(cfx_ctx* ctx, void* out, void* lse, const void* block_ou
 int cfx_attn_merge(cfx_ctx* ctx, void* out, void* lse, const void* block_out, const void* block_lse, int B, int S, int H, int D,
                    int block_out_bshd, int first, void* stream) {
     return cfx_attn_merge_wait(ctx, out, lse, block_out, block_lse, B, S, H, D, block_out_bshd, first, nullptr, 0u, stream);
+}
+
+int cfx_attn_merge_ex(cfx_ctx* ctx, void* out, void* lse, const void* block_out, const void* block_lse, int B, int S, int H, int D,
+                      int flags, const void* wait_flag, unsigned wait_value, void* final_out, void* stream) {
+    const int first = (flags & CFX_MERGE_FIRST) != 0;
+    if (!ctx || !lse || !block_out || !block_lse || (!out && !(first && final_out))) return fail(ctx, CFX_ERR_NULL, "attn_merge_ex: null pointer");
+    if (flags & ~(CFX_MERGE_BSHD | CFX_MERGE_FIRST | CFX_ELEM_BF16)) return fail(ctx, CFX_ERR_CODEC, "attn_merge_ex: unknown flag bit");
+    if (B <= 0 || S <= 0 || H <= 0 || D <= 0 || (D & 7) || D > 512) return fail(ctx, CFX_ERR_SHAPE, "attn_merge_ex: head dim must be a positive multiple of 8, at most 512");
+    if (!AL16(out) || !AL16(block_out) || !AL16(final_out)) return fail(ctx, CFX_ERR_ALIGN, "attn_merge_ex: pointers must be 16-byte aligned");
+    if (wait_flag && !ctx->gate_err && cfx_prepare(ctx) != CFX_OK) return CFX_ERR_LAUNCH;
+    if (ctx->gate_err && *(volatile unsigned*)ctx->gate_err) return fail(ctx, CFX_ERR_GATE, "attn_merge_ex: an earlier flag / gate wait on this context timed out (cfx_gate_errors)");
+    hipStream_t s = (hipStream_t)stream;
+    const int bshd = flags & CFX_MERGE_BSHD;
+    int lg = 0;
+    while ((1 << lg) < D / 8) ++lg;          // a row's D/8 threads in 2^lg lanes of one wave
+    const size_t total = ((size_t)B * S * H) << lg;
+#define MERGE_EX(E, FINAL) \
+    LAUNCH(ctx, KID_ATTN_MERGE, s, (k_attn_merge_ex<E, FINAL>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (float*)out, (float*)lse, \
+           (const u16*)block_out, (const float*)block_lse, (u16*)final_out, B, S, H, D, first, \
+           (size_t)S * H * D, bshd ? (size_t)H * D : (size_t)D, bshd ? (size_t)D : (size_t)S * D, lg, \
+           (const unsigned*)wait_flag, wait_value, ctx->gate_err, ctx->gate_timeout)
+    if (flags & CFX_ELEM_BF16) {
+        if (final_out) MERGE_EX(ElemBF16, true); else MERGE_EX(ElemBF16, false);
+    } else {
+        if (final_out) MERGE_EX(ElemF16, true); else MERGE_EX(ElemF16, false);
+    }
+#undef MERGE_EX
+    return check_launch(ctx, "attn_merge_ex launch");
 }
 
 int cfx_copy_probe(cfx_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {

@@ -229,6 +229,35 @@ __device__ __forceinline__ h16x8 el_state(bool has_base, h16x8 b, h16x8 recv) {
     }
 }
 
+// a lane's 8 elements (the raw 16-bit words) -> fp32, exact either way ...
+template <class E>
+__device__ __forceinline__ void el_widen8(h16x8 v, float (&f)[8]) {
+    if constexpr (!E::bf16) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = (float)v[k];
+    } else {
+        const u32x4 w = __builtin_bit_cast(u32x4, v);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x2 p = bf2_f32(w[i]);
+            f[2 * i] = p[0];
+            f[2 * i + 1] = p[1];
+        }
+    }
+}
+// ... and 8 fp32 values -> the element type, one rounding to nearest even each (the packed converts)
+template <class E>
+__device__ __forceinline__ h16x8 el_round8(const float (&f)[8]) {
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2 p = {f[2 * i], f[2 * i + 1]};
+        if constexpr (E::bf16) o[i] = f32_bf2(p);
+        else o[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, h16x2));
+    }
+    return __builtin_bit_cast(h16x8, o);
+}
+
 // 2-bit codes -> received values (levels +-0.5 thr, +-2 thr)
 __device__ __forceinline__ h16x8 int2_recv(u16 code, h16x8 thr) {
     h16x8 r;

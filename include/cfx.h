@@ -293,7 +293,7 @@ int    cfx_binary_rank_decompress_batch(cfx_ctx* ctx, int N, int C, int rank, in
  * sender's error-feedback update, 17-22 low-rank chain (prep, aq, aty, chol, apply, decode), 23 binary_pipe (steady-state
  * fused launch of cfx_plan_run_pipelined), 24 binary_pipe prologue / epilogue / ragged-unit launches, 25 residual2_delta,
  * 26 residual2_update, 27 absmean_compress<bits> (statistics + sign bits + in-launch finalize [+ ride-along reconstruction]),
- * 28 absmean_compress (2-bit statistics + in-launch finalize), 29 minmax_compress (int4 / int8 statistics + in-launch finalize), 30 attn_merge. */
+ * 28 absmean_compress (2-bit statistics + in-launch finalize), 29 minmax_compress (int4 / int8 statistics + in-launch finalize), 30 attn_merge (cfx_attn_merge_ex's launches too). */
 int         cfx_profile_enable(cfx_ctx* ctx, int capacity, unsigned kernel_mask, int stride);
 int         cfx_profile_read(cfx_ctx* ctx, int* kernel_ids, float* ms, int cap);
 const char* cfx_kernel_name(int kernel_id);
@@ -503,6 +503,21 @@ int cfx_attn_merge(cfx_ctx* ctx, void* out, void* lse, const void* block_out, co
                    int block_out_bshd, int first, void* stream);
 int cfx_attn_merge_wait(cfx_ctx* ctx, void* out, void* lse, const void* block_out, const void* block_lse, int B, int S, int H, int D,
                         int block_out_bshd, int first, const void* wait_flag, unsigned wait_value, void* stream);
+/* The same merge for fp16 OR bf16 blocks, with the layer's final cast in the launch.  `flags`: CFX_MERGE_BSHD (block_out is
+ * [B][S][H][D]; otherwise [B][H][S][D]), CFX_MERGE_FIRST (initialise from the block), CFX_ELEM_BF16 (block_out - and final_out - are
+ * bf16: widened to fp32 exactly, the arithmetic is the same fp32 arithmetic); any other bit is CFX_ERR_CODEC.  wait_flag / wait_value
+ * as in cfx_attn_merge_wait.
+ *   final_out == NULL   out / lse are updated exactly as cfx_attn_merge_wait updates them.
+ *   final_out != NULL   the layer's LAST block: the merged result - the very fp32 values the other form would have stored in `out` -
+ *                       is rounded to the element type (nearest even) and written to final_out, a contiguous [B][S][H][D] 16-bit
+ *                       tensor; lse is updated as usual, `out` is only read.  With CFX_MERGE_FIRST (a single block) final_out takes
+ *                       the block's own bits, lse the block's, and `out` is not touched: it may then be NULL.
+ * Checks, in this order: a NULL pointer CFX_ERR_NULL, an unknown flag bit CFX_ERR_CODEC, the shape (D % 8 == 0, D <= 512)
+ * CFX_ERR_SHAPE, 16-byte alignment of out, block_out and final_out CFX_ERR_ALIGN, a pending gate error CFX_ERR_GATE.  Finite inputs. */
+#define CFX_MERGE_BSHD 1
+#define CFX_MERGE_FIRST 2
+int cfx_attn_merge_ex(cfx_ctx* ctx, void* out, void* lse, const void* block_out, const void* block_lse, int B, int S, int H, int D,
+                      int flags, const void* wait_flag, unsigned wait_value, void* final_out, void* stream);
 
 /* Bandwidth probe: dst[i] = src[i] over `bytes` (multiple of 16) - the achievable-HBM reference
  * against which bench.py reports roofline fractions. */

@@ -1,6 +1,6 @@
 """SURVEY.md §8d protocol 2: the deployable path (`compact_fwd`, gather schedule) with REAL attention, one GPU.
 
-FLUX.1-dev shape as one rank of a ring of 8 sees it: q/k/v (1, 544, 24, 128) fp16, 57 layers, 1-bit residual codec.  The 8
+FLUX.1-dev shape as one rank of a ring of 8 sees it: q/k/v (1, 544, 24, 128) fp16 (--dtype bf16: bf16), 57 layers, 1-bit residual codec.  The 8
 logical ranks are looped back: every peer's packet is this rank's own packet (tests/fake_rccl in loopback mode stands in for
 RCCL - same stream-ordered all-gather, device copies instead of xGMI; with real peers the collective's wire time adds to what
 must hide under the local attention block).  Legs, all on the same inputs:
@@ -19,7 +19,7 @@ must hide under the local attention block).  Legs, all on the same inputs:
                  torch.distributed.all_gather_into_tensor, whose ~50 us of host time per call is NOT included here)
 Reported: wall ms/step, host issue ms/step, exposed exchange = leg - attention, host us/layer (by difference of legs: noisy;
 and the native exchange's own host calls measured directly).
-Run on the GPU box:  python tools/overlap_bench.py [--steps K] [--json out.json]
+Run on the GPU box:  python tools/overlap_bench.py [--steps K] [--dtype fp16|bf16] [--json out.json]
 """
 import argparse
 import ctypes
@@ -43,7 +43,9 @@ ap.add_argument("--preset", default="binary", choices=["binary", "int2", "lowran
                 help="the shipped preset the exchange runs (reference examples/configs.py:39-98); other than binary: the legs `attention`, "
                      "`attention_on_compute_lane`, `layer_op` (lane off: the one-call exchange on the caller's stream) and `default` "
                      "(every switch at its default: the lane for the streaming codecs, the layer op for the low-rank family)")
+ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="element type of q, k, v (bf16: the 1-bit / 2-bit presets)")
 args = ap.parse_args()
+DT = torch.bfloat16 if args.dtype == "bf16" else torch.float16
 PRESETS = {"binary": ("BINARY", dict(comp_rank=-1, fastpath=True)), "int2": ("INT2", dict(comp_rank=-1, fastpath=True)),
            "lowrank8": ("LOW_RANK", dict(comp_rank=8, fastpath=False)), "lowrank16": ("LOW_RANK", dict(comp_rank=16, fastpath=False)),
            "lowrankq32": ("LOW_RANK_Q", dict(comp_rank=32, fastpath=False))}
@@ -90,10 +92,10 @@ class LoopComm:
 Profiler.instance().disable()
 collector.init(collector.Collector("/tmp/none", enabled=False))
 g = torch.Generator(device=dev).manual_seed(1)
-qs = [torch.randn(1, N, H, D, device=dev, dtype=torch.float16, generator=g) for _ in range(L)]
-k0 = [torch.randn(1, N, H, D, device=dev, dtype=torch.float16, generator=g) for _ in range(L)]
-v0 = [torch.randn(1, N, H, D, device=dev, dtype=torch.float16, generator=g) for _ in range(L)]
-drift = [[0.1 * torch.randn(1, N, H, D, device=dev, dtype=torch.float16, generator=g) for _ in range(L)] for _ in range(2)]
+qs = [torch.randn(1, N, H, D, device=dev, dtype=DT, generator=g) for _ in range(L)]
+k0 = [torch.randn(1, N, H, D, device=dev, dtype=DT, generator=g) for _ in range(L)]
+v0 = [torch.randn(1, N, H, D, device=dev, dtype=DT, generator=g) for _ in range(L)]
+drift = [[0.1 * torch.randn(1, N, H, D, device=dev, dtype=DT, generator=g) for _ in range(L)] for _ in range(2)]
 ks = [[(k0[l] + drift[s][l]) for l in range(L)] for s in range(2)]
 vs = [[(v0[l] - drift[s][l]) for l in range(L)] for s in range(2)]
 torch.cuda.synchronize()
