@@ -48,6 +48,14 @@ def decompress(name, pkt, base_u16, N, C, param=0):
     return add_base(base_u16, R.decompress(name, pkt, N, C, param))
 
 
+def int2_quantize(x_u16, base_u16, tok16, chan16):
+    """cfx_int2_quantize with CFX_FLAG_ELEM_BF16: the scales are GIVEN (the packet tail); (packet words, new_base bf16 bits)"""
+    d = delta(x_u16, base_u16)
+    idx, thr = R.int2_codes(d, R.as_f16(tok16), R.as_f16(chan16))
+    pkt = R.fastpath_packet(R.pack_int2(idx), R.as_f16(tok16), R.as_f16(chan16))
+    return pkt, add_base(base_u16, R.int2_levels(idx, thr))
+
+
 def torch_bits(t):
     """uint16 bit patterns of a 16-bit torch tensor (fp16 or bf16), on the host."""
     import torch
