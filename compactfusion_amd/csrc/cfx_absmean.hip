@@ -694,13 +694,62 @@ __device__ __forceinline__ void absmean_last_arriver_jobs(const cfx_comp_item& i
 #undef STAMP
 }
 
-// The layer launches' jobs on TAGGED partials (put_tagged): no last arriver - a FIXED workgroup per job, the last-dispatched tiles of the
-// tensor (V of column block bx: tile (bx, P - 1); U: tile (CB - 1, P - 2)), polls the very words it reduces until all carry the
-// launch's tag.  Fourteen workgroups polling ~70 KB a round is nothing beside the launch's traffic (every TILE polling was: the min/max
-// layer's first form).  A thread's loads of a round are issued together, then the tags compared (a test per load serialises them).
-// Arithmetic = absmean_last_arriver_jobs (exact integer sums: bit-identical for any order).  do_col / do_row: uniform per workgroup.
+// The layer launches' jobs on TAGGED partials (put_tagged): no last arriver - FIXED workgroups, the last-dispatched tiles of the tensor, poll
+// the very words they reduce until all carry the launch's tag.  A thread's loads of a round are issued together, then the tags compared (a
+// test per load serialises them).  Arithmetic = absmean_last_arriver_jobs (exact integer sums: bit-identical for any order and any split).
+//
+// V of column block bx is SPLIT over sv workgroups (sv in {1, 2, 4}, chosen by the host: scale_jobs_split): sub-job k, on tile
+// (bx, P - 1 - k), owns the TILE_C / sv contiguous channels  bx * TILE_C + k * cw ..  and all P partials of each.  Its 512 threads are
+// cw channels x sv partial groups (group g: partials [g * L, (g + 1) * L), L = ceil(P / sv)), combined through LDS - so a wave asks for
+// 64 x L words a round whatever sv is, 4.6 KB at the FLUX shard with sv = 2 where one workgroup asked for 8.75 KB a wave (a hand-off
+// beyond ~4 KB per consumer wave stops being one fabric hop, MI355X_MICROARCH.md "handoff-payload").  Every sub-job polls, stores its
+// part of V, drains and arrives by itself; a sub-job whose channels lie wholly beyond C does not exist (neither run nor counted:
+// scale_jobs_arrivals).  U runs on a tile of its own, (CB - 1, P - 1 - sv), or - a one-tile-high tensor - after the V job of tile (CB - 1, 0).
+//
+// No deadlock: a statistics tile publishes its partials before it polls anything, and only the reducers poll.  They wait for tiles
+// dispatched after them as well (the U job always did), so what has to hold is that the reducers of a launch can never fill every
+// workgroup slot of the stream while a tile they wait for is still undispatched: dispatch is in order, every non-reducer in front of
+// that tile retires without waiting, and the host keeps batch * (CB * sv + 1) far below the slots of the smallest stream that runs a
+// layer launch (SCALE_JOBS_MAX_SPLIT_REDUCERS = 64 against 128 CUs; the 2-bit launch has all statistics tiles co-resident anyway).
+//
+// The fp16 scales leave as 16-byte write-through stores, 8 channels / 8 rows each, transposed through LDS like the sign bits (a 2-byte
+// write-through store costs a fabric write of its own, 1024 of them per V job) wherever the packet's section is 16-byte aligned - V
+// starts 2 N bytes behind U, so N % 8 decides - and per element otherwise (uniform branch; the ragged last rows of U always).
+// TAGGED_COPIES: the tagged copies ta.tV / ta.tU are stored only in launches whose workgroups poll them (the 2-bit launch; the 1-bit
+// launch under ONEBIT_D_TAGGED).  LDS: sm[0] V's partial groups, sm[1] U's wave totals, sm[2] the fp16 staging (rows below FUSED_NW:
+// free once the tile's statistics are out, clear of the 2-bit kernel's parked rows sm[FUSED_NW ..] and its s16).
+// FUSED_CH_1BIT: the widest round of the 1-bit kernel.  With 13 words and more in flight the V job, not the reconstruction tile, sets the
+// kernel's registers (101 VGPRs / 100 SGPRs instead of the 100 / 95 the kernel has had: tests/golden/resource_rows_parent.json pins them);
+// the split keeps a round at 9 words wherever it applies, so only an unsplit job of 13 .. 18 partials - the reducer bound at a large
+// batch - takes a second round for it.  The 2-bit kernel (117 VGPRs either way) keeps FUSED_CH.
+#ifndef FUSED_CH_1BIT
+#define FUSED_CH_1BIT 12
+#endif
+template <int CH>
+__device__ __forceinline__ void tagged_col_rounds(const TagArena& ta, const u64* colpart, int C, int cc, int p0, int p1, SpinClock& clk,
+                                                  long long timeout, bool& failed, u64& a) {
+    for (int p = p0; p < p1 && !failed; p += CH) {
+        u64 v[CH];
+        for (;;) {
+#pragma unroll
+            for (int j = 0; j < CH; ++j) v[j] = ld_wt(&ta.tcol[(size_t)min(p + j, p1 - 1) * C + cc]);
+            bool ok = true;
+#pragma unroll
+            for (int j = 0; j < CH; ++j) ok = ok && tag_is(v[j], ta.tagbits);
+            if (ok) break;
+            __builtin_amdgcn_s_sleep(2);
+            if (clk.expired(timeout)) { failed = true; break; }
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const u64 w = v[j] & TAG_SAT;
+            if (p + j < p1) a += (w == TAG_SAT && !failed) ? ld_wt(&colpart[(size_t)(p + j) * C + cc]) : w;      // rare: the exact sum beside it
+        }
+    }
+}
+template <bool TAGGED_COPIES>
 __device__ __forceinline__ void absmean_tagged_jobs(const cfx_comp_item& it, int N, int C, int CB, int P, int bx, u64* rowpart, const TagArena& ta,
-                                                    int per_byte, int eps_mode, u64 (*sm)[TILE_C], bool do_col, bool do_row, Probe probe,
+                                                    int per_byte, int eps_mode, u64 (*sm)[TILE_C], int sv, int v_sub, bool do_row, Probe probe,
                                                     unsigned* gate, unsigned* err, long long timeout) {
     constexpr int NT = FUSED_NT;
 #define STAMP(k) probe.at(k)
@@ -709,38 +758,39 @@ __device__ __forceinline__ void absmean_tagged_jobs(const cfx_comp_item& it, int
     const u64* colpart = rowpart + (size_t)N * CB;
     h16* U = (h16*)((char*)it.packet + (size_t)N * (C / per_byte));
     h16* V = U + N;
+    u16* stage = (u16*)&sm[2][0];
     SpinClock clk;
     bool failed = false;
 #define PUT16(ptr, val) st_wt((u16*)(ptr), hbits(val))
-    if (do_col) {
-        // V of column block bx: one column per thread, FUSED_CH partials a round
-        const int c = bx * TILE_C + tid, cc = min(c, C - 1);
+    if (v_sub >= 0) {
+        const int cw = TILE_C / sv;                                  // channels of the sub-job; tid = g * cw + ch
+        const int ch = tid & (cw - 1), g = __builtin_amdgcn_readfirstlane(tid / cw);      // (cw >= 128: a wave is in one group)
+        const int c0 = bx * TILE_C + v_sub * cw;
+        const int cc = min(c0 + ch, C - 1);
+        const int L = (P + sv - 1) / sv;
+        const int p0 = min(g * L, P), p1 = min(p0 + L, P);
         u64 a = 0;
-        for (int p0 = 0; p0 < P && !failed; p0 += FUSED_CH) {
-            u64 v[FUSED_CH];
-            for (;;) {
-#pragma unroll
-                for (int j = 0; j < FUSED_CH; ++j) v[j] = ld_wt(&ta.tcol[(size_t)min(p0 + j, P - 1) * C + cc]);
-                bool ok = true;
-#pragma unroll
-                for (int j = 0; j < FUSED_CH; ++j) ok = ok && tag_is(v[j], ta.tagbits);
-                if (ok) break;
-                __builtin_amdgcn_s_sleep(2);
-                if (clk.expired(timeout)) { failed = true; break; }
-            }
-#pragma unroll
-            for (int j = 0; j < FUSED_CH; ++j) {
-                const u64 w = v[j] & TAG_SAT;
-                if (p0 + j < P) a += (w == TAG_SAT && !failed) ? ld_wt(&colpart[(size_t)(p0 + j) * C + cc]) : w;      // rare: the exact sum beside it
-            }
-        }
+        if (L <= 5) tagged_col_rounds<5>(ta, colpart, C, cc, p0, p1, clk, timeout, failed, a);
+        else if (L <= 9) tagged_col_rounds<9>(ta, colpart, C, cc, p0, p1, clk, timeout, failed, a);
+        else tagged_col_rounds<TAGGED_COPIES ? FUSED_CH : FUSED_CH_1BIT>(ta, colpart, C, cc, p0, p1, clk, timeout, failed, a);
         STAMP(4);
+        u64* grp = &sm[0][0];
+        grp[tid] = a;
         failed = __syncthreads_or(failed ? 1 : 0) != 0;
         if (!failed) {
-            if (c < C) {
-                const h16 vm = mean16(a, N);
-                st_wt(&ta.tV[c], ta.tagbits | (u64)hbits(vm));      // first: the copy the launch's own reconstruction workgroups poll
-                PUT16(&V[c], vm);
+            const bool packed = ((uintptr_t)(V + c0) & 15) == 0 && (C & 7) == 0;      // uniform
+            const int c = c0 + tid;
+            if (tid < cw && c < C) {
+                u64 tot = 0;
+                for (int q = 0; q < sv; ++q) tot += grp[q * cw + tid];
+                const h16 vm = mean16(tot, N);
+                if (TAGGED_COPIES) st_wt(&ta.tV[c], ta.tagbits | (u64)hbits(vm));      // first: the copy the launch's own workgroups poll
+                if (packed) stage[tid] = hbits(vm);
+                else PUT16(&V[c], vm);
+            }
+            if (packed) {
+                lds_barrier();
+                if (tid < cw / 8 && c0 + 8 * tid + 8 <= C) st16_wt(V + c0 + 8 * tid, *(const u32x4*)(stage + 8 * tid));
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             lds_barrier();
@@ -749,39 +799,52 @@ __device__ __forceinline__ void absmean_tagged_jobs(const cfx_comp_item& it, int
         STAMP(5);
     }
     if (do_row && !failed) {
-        // U: one row per thread and pass; its CB partials in one round
+        // U: a thread's two rows (tid, tid + NT) and FUSED_RCH column blocks of both in ONE round - 12 words in flight, every load
+        // unconditional (clamped index, masked value; a wave with no second row skips that half); beyond 2 NT rows, batches of two rows
         u64* smem = &sm[1][0];
-        auto row_sum = [&](int n) {
-            const int nc = min(n, N - 1);
-            u64 s_ = 0;
+        auto row_sums2 = [&](int n0, int n1, bool two, u64& s0, u64& s1) {
+            const int m0 = min(n0, N - 1), m1 = min(n1, N - 1);
+            s0 = s1 = 0;
             for (int k0 = 0; k0 < CB && !failed; k0 += FUSED_RCH) {
-                u64 q[FUSED_RCH];
+                u64 q0[FUSED_RCH], q1[FUSED_RCH];
                 for (;;) {
 #pragma unroll
-                    for (int j = 0; j < FUSED_RCH; ++j) q[j] = ld_wt(&ta.trow[(size_t)min(k0 + j, CB - 1) * N + nc]);
+                    for (int j = 0; j < FUSED_RCH; ++j) q0[j] = ld_wt(&ta.trow[(size_t)min(k0 + j, CB - 1) * N + m0]);
+                    if (two) {
+#pragma unroll
+                        for (int j = 0; j < FUSED_RCH; ++j) q1[j] = ld_wt(&ta.trow[(size_t)min(k0 + j, CB - 1) * N + m1]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < FUSED_RCH; ++j) q1[j] = ta.tagbits;
+                    }
                     bool ok = true;
 #pragma unroll
-                    for (int j = 0; j < FUSED_RCH; ++j) ok = ok && tag_is(q[j], ta.tagbits);
+                    for (int j = 0; j < FUSED_RCH; ++j) ok = ok && tag_is(q0[j], ta.tagbits) && tag_is(q1[j], ta.tagbits);
                     if (ok) break;
                     __builtin_amdgcn_s_sleep(2);
                     if (clk.expired(timeout)) { failed = true; break; }
                 }
 #pragma unroll
                 for (int j = 0; j < FUSED_RCH; ++j) {
-                    const u64 w = q[j] & TAG_SAT;
-                    if (k0 + j < CB) s_ += (w == TAG_SAT && !failed) ? ld_wt(&rowpart[(size_t)(k0 + j) * N + nc]) : w;
+                    const u64 w0 = q0[j] & TAG_SAT, w1 = q1[j] & TAG_SAT;
+                    if (k0 + j < CB) {
+                        s0 += (w0 == TAG_SAT && !failed) ? ld_wt(&rowpart[(size_t)(k0 + j) * N + m0]) : w0;
+                        s1 += (w1 == TAG_SAT && !failed) ? ld_wt(&rowpart[(size_t)(k0 + j) * N + m1]) : w1;
+                    }
                 }
             }
-            return s_;
         };
         // pass 1: every row's fp16 mean -> the sum of the means (the tensor's grand mean); a thread keeps its first two rows' means
         h16 h0 = (h16)0, h1 = (h16)0;
         u64 acc = 0;
-        for (int n0 = tid, i = 0; n0 - tid < N; n0 += NT, ++i) {
-            const h16 h = mean16(row_sum(n0), C);
-            if (i == 0) h0 = h;
-            if (i == 1) h1 = h;
-            if (n0 < N) acc += habs_units(hbits(h));
+        for (int b0 = 0; b0 < N; b0 += 2 * NT) {
+            const int n0 = b0 + tid, n1 = n0 + NT;
+            u64 s0, s1;
+            row_sums2(n0, n1, (n1 & ~63) < N, s0, s1);
+            const h16 ha = mean16(s0, C), hb = mean16(s1, C);
+            if (b0 == 0) { h0 = ha; h1 = hb; }
+            if (n0 < N) acc += habs_units(hbits(ha));
+            if (n1 < N) acc += habs_units(hbits(hb));
         }
         STAMP(13);
         const u64 wtot = wave_sum_u64(acc);
@@ -794,11 +857,34 @@ __device__ __forceinline__ void absmean_tagged_jobs(const cfx_comp_item& it, int
             for (int w = 0; w < NT / 64; ++w) tot += smem[w];
             const h16 mu = mean16(tot, N);
             const float den = eps_mode ? (float)(h16)((float)mu + 1e-6f) : (float)mu;
-            for (int n0 = tid, i = 0; n0 < N; n0 += NT, ++i) {
-                const h16 h = i == 0 ? h0 : (i == 1 ? h1 : mean16(row_sum(n0), C));      // (beyond 2 NT rows: the partials are read again)
-                const h16 un = (h16)((float)h / den);
-                st_wt(&ta.tU[n0], ta.tagbits | (u64)hbits(un));
-                PUT16(&U[n0], un);
+            const bool packed = ((uintptr_t)U & 15) == 0;                // uniform
+            for (int b0 = 0; b0 < N; b0 += 2 * NT) {
+                const int n0 = b0 + tid, n1 = n0 + NT;
+                h16 ha = h0, hb = h1;
+                if (b0) {                                                  // (beyond 2 NT rows: the partials are read again - all tagged by now)
+                    u64 s0, s1;
+                    row_sums2(n0, n1, (n1 & ~63) < N, s0, s1);
+                    ha = mean16(s0, C); hb = mean16(s1, C);
+                }
+                const h16 ua = (h16)((float)ha / den), ub = (h16)((float)hb / den);
+                if (TAGGED_COPIES) {
+                    if (n0 < N) st_wt(&ta.tU[n0], ta.tagbits | (u64)hbits(ua));
+                    if (n1 < N) st_wt(&ta.tU[n1], ta.tagbits | (u64)hbits(ub));
+                }
+                if (packed) {
+                    if (b0) lds_barrier();                                 // the previous batch's staging has been read
+                    stage[tid] = hbits(ua);
+                    stage[tid + NT] = hbits(ub);
+                    lds_barrier();
+                    const int r = b0 + 8 * tid;                            // 2 NT rows = 128 groups of 8
+                    if (tid < 2 * NT / 8 && r < N) {
+                        if (r + 8 <= N) st16_wt(U + r, *(const u32x4*)(stage + 8 * tid));
+                        else for (int i = r; i < N; ++i) st_wt((u16*)&U[i], stage[i - b0]);
+                    }
+                } else {
+                    if (n0 < N) PUT16(&U[n0], ua);
+                    if (n1 < N) PUT16(&U[n1], ub);
+                }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             lds_barrier();
@@ -886,7 +972,7 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
                                                    u64* rowpart, unsigned* tick, int per_byte, int eps_mode, u64 (*sm)[TILE_C], int dbg,
                                                    Probe probe, unsigned* gate = nullptr, unsigned gate_expect = 0, int flags = 0,
                                                    unsigned* gate2 = nullptr, unsigned expect2 = 0, unsigned* err = nullptr, long long timeout = 0,
-                                                   TagArena ta = TagArena()) {
+                                                   TagArena ta = TagArena(), int sv = 1) {
     // developer probes (cfx_dev.h): per-workgroup phase times, 100 MHz wall clock
 #define STAMP(k) probe.at(k)
     STAMP(0);
@@ -915,8 +1001,10 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
     STAMP(1);
     if constexpr (GATED) {
         // the layer launches: tagged partials, fixed reducers (absmean_tagged_jobs) - nothing to drain, no ticket to draw
-        const bool v_wg = by == P - 1;
-        const bool u_wg = P >= 2 ? (by == P - 2 && bx == CB - 1) : (bx == CB - 1);
+        // (sv <= max(1, P - 1): only a one-tile-high tensor runs U behind a V job)
+        const int v_k = P - 1 - by;
+        const bool v_wg = v_k < sv && bx * TILE_C + v_k * (TILE_C / sv) < C;
+        const bool u_wg = bx == CB - 1 && by == max(P - 1 - sv, 0);
         probe.copy(2, 1); probe.copy(3, 1); probe.set(7, (v_wg ? 1 : 0) | (u_wg ? 2 : 0));
         if (v_wg || u_wg) {
             // KEEP: the jobs' loads in flight beside the whole tile do not fit 128 registers (tools/resource_usage.py, tests/test_resource_usage.py)
@@ -927,7 +1015,8 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
                 park[threadIdx.x] = __builtin_bit_cast(u32x4, xk[US - 1]);
                 park[FUSED_NT + threadIdx.x] = __builtin_bit_cast(u32x4, bk[US - 1]);
             }
-            absmean_tagged_jobs(it, N, C, CB, P, bx, rowpart, ta, per_byte, eps_mode, sm, v_wg, u_wg, probe, gate, err, timeout);
+            absmean_tagged_jobs<KEEP || ONEBIT_D_TAGGED>(it, N, C, CB, P, bx, rowpart, ta, per_byte, eps_mode, sm, sv, v_wg ? v_k : -1, u_wg, probe, gate,
+                                                         err, timeout);
             if constexpr (KEEP) {
                 xk[US - 1] = __builtin_bit_cast(h16x8, park[threadIdx.x]);
                 bk[US - 1] = __builtin_bit_cast(h16x8, park[FUSED_NT + threadIdx.x]);
@@ -1009,6 +1098,7 @@ struct FusedArgs {
     unsigned* xgate;
     unsigned xexpect;
     int remote;              // the gated items' packets may sit in a peer GPU's memory (read with system-scope loads)
+    int sv;                  // GATED: workgroups a column block's V job is split over (scale_jobs_split)
     P2PInline p2p;           // own != NULL: workgroup 0 runs the peer-to-peer exchange and opens xgate itself
 };
 #ifndef GATE_WPE
@@ -1031,7 +1121,7 @@ __global__ __launch_bounds__(FUSED_NT, GATE_WPE) __attribute__((amdgpu_num_vgpr(
         absmean_fused_body<EMIT_BITS, US, GATED, false, E>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
                                                  a.tick + z * TICK_WORDS, a.per_byte, a.eps_mode, sm, a.dbg,
                                                  a.probe.of(b), a.gate, a.gate_expect, 0, nullptr, 0u, a.gate_err, a.timeout,
-                                                 tag_arena_of(a.tarena, a.tarena_stride, z, a.N, a.C, a.CB, a.P, a.tag));
+                                                 tag_arena_of(a.tarena, a.tarena_stride, z, a.N, a.C, a.CB, a.P, a.tag), GATED ? a.sv : 1);
         if constexpr (GATED) {
             if (b == 0 && a.p2p.own) p2p_exchange_inline(a.gate, a.gate_expect, 1, a.p2p, a.xgate, a.xexpect, a.gate_err);
         }
@@ -1334,6 +1424,7 @@ struct Int2LayerArgs {
     signed char src[CFX_MAX_BATCH];                        // gated item -> the own tensor of this launch whose packet it reads, or -1
     unsigned* xgate; unsigned xexpect;     // external gate for group D (exchange-layer op): NULL = group D waits on gate2
     int remote;                            // group D's packets may sit in a peer GPU's memory
+    int sv;                                // workgroups a column block's V job is split over (scale_jobs_split)
     P2PInline p2p;                         // own != NULL: workgroup 0 runs the peer-to-peer exchange and opens xgate itself
 };
 template <int US, class E>
@@ -1347,7 +1438,7 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_int2_compress_gated(BatchC batc
         const int by = rem / a.CB;
         absmean_fused_body<false, US, true, true, E>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
                                                   a.tick + z * TICK_WORDS, 4, 1, sm, 0, Probe(), a.gate1, a.expect1, a.flags, a.gate2, a.expect2, a.err, a.timeout,
-                                                  tag_arena_of(a.tarena, a.tarena_stride, z, a.N, a.C, a.CB, a.P, a.tag));
+                                                  tag_arena_of(a.tarena, a.tarena_stride, z, a.N, a.C, a.CB, a.P, a.tag), a.sv);
         // (packets complete = the codes gate's last arriver has written the "open" words: XCD 0's)
         if (b == 0 && a.p2p.own) p2p_exchange_inline(a.gate2 + 1 * GATE_LINE, a.expect2, 1, a.p2p, a.xgate, a.xexpect, a.err);
         return;
@@ -1417,6 +1508,29 @@ static unsigned abs_arena_for(cfx_ctx* ctx, unsigned ring, void* stream, size_t 
     }
     *arena = ctx->abs_arena[ring];
     return tag;
+}
+
+// How many workgroups share a column block's V job in the layer launches (absmean_tagged_jobs), from {1, 2, 4}: the smallest split that
+// brings a wave's poll round to about 4 KB - 64 lanes x ceil(P / sv) tagged words, at most 9 words a lane - lowered while the launch
+// would have more than SCALE_JOBS_MAX_SPLIT_REDUCERS reducers (each one is an arrival on the gate's counter line, which 8 relays poll,
+// and a workgroup that waits: see the no-deadlock note there) and never beyond max(1, P - 1), so that U keeps a tile of its own.
+#ifndef SCALE_JOBS_MAX_SPLIT_REDUCERS
+#define SCALE_JOBS_MAX_SPLIT_REDUCERS 64
+#endif
+#ifndef SCALE_JOBS_ROUND_WORDS
+#define SCALE_JOBS_ROUND_WORDS 9
+#endif
+static int scale_jobs_split(const cfx_ctx* ctx, int CB, int P, int batch) {
+    int sv = 1;
+    while (sv < 4 && (P + sv - 1) / sv > SCALE_JOBS_ROUND_WORDS) sv *= 2;
+    if (ctx->dev_scale_split) sv = ctx->dev_scale_split;      // the developer library's sweep switch (include/cfx_dev.h); 0 in the product library
+    while (sv > 1 && (batch * (CB * sv + 1) > SCALE_JOBS_MAX_SPLIT_REDUCERS || sv > std::max(1, P - 1))) sv /= 2;
+    return sv;
+}
+// arrivals the jobs of one launch put on its scales gate: per tensor one for U and one per V sub-job that owns a channel
+static unsigned scale_jobs_arrivals(int C, int sv, int batch) {
+    const int cw = TILE_C / sv;
+    return (unsigned)batch * (unsigned)((C + cw - 1) / cw + 1);
 }
 
 int cfx_i_absmean_compress(CompressCall& cc) {
@@ -1498,7 +1612,8 @@ int cfx_i_absmean_compress(CompressCall& cc) {
         a.flags = flags; a.ws = ws; a.ws_stride = wstride; a.tick = tick;
         a.gate1 = ctx->gate + (size_t)slot * GATE_STRIDE;
         a.gate2 = a.gate1 + GATE_BLOCK;
-        ctx->gate_expect[3 * slot] += (unsigned)batch * (unsigned)(CB + 1);
+        a.sv = scale_jobs_split(ctx, CB, P, batch);
+        ctx->gate_expect[3 * slot] += scale_jobs_arrivals(C, a.sv, batch);
         ctx->gate_expect[3 * slot + 1] += (unsigned)a.n_st;
         a.expect1 = ctx->gate_expect[3 * slot]; a.expect2 = ctx->gate_expect[3 * slot + 1];
         a.err = ctx->gate_err;
@@ -1554,7 +1669,8 @@ int cfx_i_absmean_compress(CompressCall& cc) {
             a.g_R = ((N + a.g_rb - 1) / a.g_rb + FUSED_NW - 1) / FUSED_NW * FUSED_NW;
             a.n_gt = a.n_g = CB * a.g_rb * n_gated_k;
             a.gate = ctx->gate + (size_t)slot * GATE_STRIDE;
-            ctx->gate_expect[3 * slot] += (unsigned)batch * (unsigned)(CB + 1);
+            a.sv = scale_jobs_split(ctx, CB, P, batch);
+            ctx->gate_expect[3 * slot] += scale_jobs_arrivals(C, a.sv, batch);
             a.gate_expect = ctx->gate_expect[3 * slot];
             a.tarena_stride = tag_arena_words(N, C, CB, P);
             a.tag = abs_arena_for(ctx, slot / TICK_RING, stream, a.tarena_stride * batch * sizeof(u64), &a.tarena);

@@ -251,6 +251,7 @@ cfx_ctx* cfx_create(int device) {
     c->gated_on = 1;
     c->lr_chain = c->lr_decode = 0;
     c->dev_probe = 0;
+    c->dev_scale_split = 0;
     c->allow_shared_queues = 0;
     c->ipc_kind = 0;
     c->ipc_want = 2;
@@ -310,6 +311,12 @@ int cfx_dev_set_launch_tags(cfx_ctx* ctx, unsigned abs_seq, unsigned mml_seq) {
 
 int cfx_dev_set_probe(cfx_ctx* ctx, int mode) {
     if (!ctx) return CFX_ERR_NULL;
+    if (mode >= 0x100) {                              // CFX_DEV_SCALE_SPLIT + s (include/cfx_dev.h)
+        const int sv = mode - 0x100;
+        if (sv != 0 && sv != 1 && sv != 2 && sv != 4) return fail(ctx, CFX_ERR_BATCH, "scale split must be 0, 1, 2 or 4");
+        ctx->dev_scale_split = sv;
+        return CFX_OK;
+    }
     if (mode < 0 || mode > 4) return fail(ctx, CFX_ERR_BATCH, "dev probe must be 0..4");
     ctx->dev_probe = mode;
     return CFX_OK;

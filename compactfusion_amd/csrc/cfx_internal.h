@@ -96,6 +96,7 @@ struct cfx_ctx {
     int gated_on;                   // cfx_set_gated_launch: 1 (default) the one-launch gated / exchange-layer forms where they qualify
     int lr_chain, lr_decode;        // cfx_set_lr_chain / cfx_set_lr_decode (0 = automatic)
     int dev_probe;                  // cfx_set_dev_probe (developer builds)
+    int dev_scale_split;            // cfx_dev_set_probe(CFX_DEV_SCALE_SPLIT + s) (developer builds): 0 = the library's choice
     int allow_shared_queues;        // cfx_set_allow_shared_queues: flag-ordered streams even when cfx_hw_queues_ok() == 0
     int ipc_want;                   // cfx_set_ipc_memory_kind: what cfx_ipc_alloc asks for first (2 uncached - default -, 1 fine-grained, 0 ordinary)
     int ipc_kind;                   // what the last cfx_ipc_alloc returned: 2 uncached, 1 fine-grained, 0 ordinary device memory

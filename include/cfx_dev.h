@@ -18,7 +18,11 @@ int cfx_dev_stamps(cfx_ctx* ctx, void* buf);
  * over.  This sets the two counters (after a device synchronisation) so that a test can walk a context across the wrap. */
 int cfx_dev_set_launch_tags(cfx_ctx* ctx, unsigned abs_seq, unsigned mml_seq);
 /* Early exits of the one-launch compress kernel (tools/fused_probe.py): 1 = stop after publishing, 2 = after the tickets, 3 = empty grid,
- * 4 = loads only; 0 = off. */
+ * 4 = loads only; 0 = off.
+ * CFX_DEV_SCALE_SPLIT + s, s in {0, 1, 2, 4}: leaves the probe mode alone and makes the 1-bit / 2-bit layer launches split a column block's
+ * channel-scale job over s workgroups where the shape allows it (csrc/cfx_absmean.hip scale_jobs_split), instead of the split the library
+ * chooses; s = 0 gives the choice back.  For the sweep behind profiles/scale_jobs_split_sweep.md - the split is no product knob. */
+#define CFX_DEV_SCALE_SPLIT 0x100
 int cfx_dev_set_probe(cfx_ctx* ctx, int mode);
 
 #ifdef __cplusplus
