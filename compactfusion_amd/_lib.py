@@ -32,6 +32,11 @@ class DecompItem(ctypes.Structure):
     _fields_ = [("packet", ctypes.c_void_p), ("base", ctypes.c_void_p), ("recon", ctypes.c_void_p)]
 
 
+class SecondItem(ctypes.Structure):
+    """cfx_second_item: the second-order states of one item (include/cfx.h, "Second-order residual")"""
+    _fields_ = [("delta_base", ctypes.c_void_p), ("new_delta_base", ctypes.c_void_p)]
+
+
 # every symbol include/cfx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cfx_abi_version", ctypes.c_int, []),
@@ -128,6 +133,13 @@ SYMBOLS = [
     ("cfx_plan_finalize", ctypes.c_int, [ctypes.c_void_p]),
     ("cfx_residual2_delta", ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]),
     ("cfx_residual2_update", ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p]),
+    ("cfx_compress_batch_res2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.POINTER(CompItem), ctypes.POINTER(SecondItem), ctypes.c_float,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("cfx_decompress_batch_res2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(DecompItem), ctypes.POINTER(SecondItem), ctypes.c_float, ctypes.c_void_p]),
+    ("cfx_plan_set_second_order", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SecondItem), ctypes.c_int,
+                                                 ctypes.POINTER(SecondItem), ctypes.c_float]),
     ("cfx_attn_merge", ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
     ("cfx_copy_probe", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("cfx_binary_rank_packet_bytes", ctypes.c_size_t, [ctypes.c_int] * 3),

@@ -12,7 +12,7 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import CFX_MAX_BATCH, ELEM_BF16, FLAG_NO_EF, FLAG_UPDATE_CACHE, CfxError, CompItem, DecompItem
+from ._lib import CFX_MAX_BATCH, ELEM_BF16, FLAG_NO_EF, FLAG_UPDATE_CACHE, CfxError, CompItem, DecompItem, SecondItem
 
 
 class Codec(IntEnum):
@@ -302,6 +302,83 @@ def residual2_update(base: torch.Tensor, delta_base: torch.Tensor, recv: torch.T
     rc = _lib.load().cfx_residual2_update(ctx, _ptr(base), _ptr(delta_base), _ptr(recv), _ptr(new_base), _ptr(new_delta_base),
                                           float(decay), n, _stream_handle(stream, dev))
     _check(ctx, rc, "cfx_residual2_update")
+
+
+def res2_fused(codec: int, *tensors: Optional[torch.Tensor]) -> bool:
+    """Whether a second-order (CompactConfig(residual=2)) call on these tensors takes the fused form - `compress_batch_res2` /
+    `decompress_batch_res2`, the predictor inside the codec's own launches - instead of `residual2_delta` ; codec ; `residual2_update`:
+    the 1-bit and 2-bit codecs on CUDA fp16 tensors (include/cfx.h, "Second-order residual").  Every other codec, and tensors that are
+    not on a GPU (the stand-in backends of the CPU tests), take the composition."""
+    if int(codec) not in (int(Codec.BINARY), int(Codec.INT2)):
+        return False
+    ts = [t for t in tensors if t is not None]
+    return bool(ts) and all(t.is_cuda and t.dtype == torch.float16 for t in ts)
+
+
+def _second_items(B: int, N: int, C: int, delta_bases, new_delta_bases, need_new: bool):
+    second = (SecondItem * B)()
+    for i in range(B):
+        if delta_bases[i] is None:
+            raise ValueError("second-order call without a delta_base")
+        _check_nc(delta_bases[i], N, C, "delta_base")
+        nd = new_delta_bases[i]
+        if nd is not None:
+            _check_nc(nd, N, C, "new_delta_base")
+        elif need_new:
+            raise ValueError("update_cache needs a new_delta_base")
+        second[i] = SecondItem(_ptr(delta_bases[i]), _ptr(nd))
+    return second
+
+
+def compress_batch_res2(codec: int, xs: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], delta_bases: Sequence[torch.Tensor],
+                        new_bases: Sequence[Optional[torch.Tensor]], new_delta_bases: Sequence[Optional[torch.Tensor]],
+                        packets: Sequence[torch.Tensor], N: int, C: int, decay: float, param: int = 0, update_cache: bool = True,
+                        stream: Optional[torch.cuda.Stream] = None, ws: Optional[torch.Tensor] = None) -> None:
+    """Second-order compress of a batch in the codec's own launches (1-bit / 2-bit, fp16): packet_i of (x_i - base_i) - delta_base_i
+    and, with update_cache, new_base_i = (base_i + delta_base_i) + recv_i, new_delta_base_i = (delta_base_i + recv_i) * decay from the
+    call's own packet.  new_base / new_delta_base may be base / delta_base themselves."""
+    B = len(xs)
+    if not (1 <= B <= CFX_MAX_BATCH):
+        raise ValueError(f"batch {B} out of range 1..{CFX_MAX_BATCH}")
+    dev = _device_index(xs[0])
+    ctx = context(dev)
+    items = (CompItem * B)()
+    for i in range(B):
+        _check_nc(xs[i], N, C, "x")
+        _check_nc(bases[i], N, C, "base")
+        if new_bases[i] is not None:
+            _check_nc(new_bases[i], N, C, "new_base")
+        _device_index(packets[i])
+        items[i] = CompItem(_ptr(xs[i]), _ptr(bases[i]), _ptr(new_bases[i]) if update_cache else None, _ptr(packets[i]))
+    second = _second_items(B, N, C, delta_bases, new_delta_bases if update_cache else [None] * B, update_cache)
+    sh = _stream_handle(stream, dev)
+    if ws is None:
+        ws = workspace(codec, N, C, param, B, dev, sh)
+    rc = _lib.load().cfx_compress_batch_res2(ctx, int(codec), N, C, param, FLAG_UPDATE_CACHE if update_cache else 0, B, items, second,
+                                             float(decay), _ptr(ws), 0 if ws is None else ws.numel(), sh)
+    _check(ctx, rc, "cfx_compress_batch_res2")
+
+
+def decompress_batch_res2(codec: int, packets: Sequence[torch.Tensor], bases: Sequence[torch.Tensor], delta_bases: Sequence[torch.Tensor],
+                          recons: Sequence[torch.Tensor], new_delta_bases: Sequence[Optional[torch.Tensor]], N: int, C: int, decay: float,
+                          param: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
+    """Second-order reconstruction of a batch, one launch: recon_i = (base_i + delta_base_i) + decode(packet_i) and, where
+    new_delta_base_i is given, (delta_base_i + decode(packet_i)) * decay.  recon / new_delta_base may be base / delta_base themselves;
+    new_delta_base None: the reconstruction alone (update_cache=False)."""
+    B = len(packets)
+    if not (1 <= B <= CFX_MAX_BATCH):
+        raise ValueError(f"batch {B} out of range 1..{CFX_MAX_BATCH}")
+    dev = _device_index(recons[0])
+    ctx = context(dev)
+    items = (DecompItem * B)()
+    for i in range(B):
+        _check_nc(recons[i], N, C, "recon")
+        _check_nc(bases[i], N, C, "base")
+        _device_index(packets[i])
+        items[i] = DecompItem(_ptr(packets[i]), _ptr(bases[i]), _ptr(recons[i]))
+    second = _second_items(B, N, C, delta_bases, new_delta_bases, False)
+    rc = _lib.load().cfx_decompress_batch_res2(ctx, int(codec), N, C, param, B, items, second, float(decay), _stream_handle(stream, dev))
+    _check(ctx, rc, "cfx_decompress_batch_res2")
 
 
 def copy_probe(dst: torch.Tensor, src: torch.Tensor, stream: Optional[torch.cuda.Stream] = None) -> None:

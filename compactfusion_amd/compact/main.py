@@ -17,7 +17,9 @@ Semantics kept from the reference (file:line = xfuser/compact/main.py):
   WARMUP stores the activation as the new base and sends it raw (:195-209, :351-366); residual 0 compresses the
   activation itself (:214-226, :371-372); residual 1 compresses act - base and sets base <- base + decode(packet)
   when error feedback is on, base <- act otherwise (:227-243, :373-377); residual 2 adds the decayed second-order
-  predictor (:244-266, :378-384; `cfx_residual2_delta` / `cfx_residual2_update` around the codec, states in place); `simulate` ships the dequantised tensor (:117-119, :126-127); the fastpath accepts
+  predictor (:244-266, :378-384; 1-bit / 2-bit on fp16 GPU tensors: ONE fused call per tensor, `cfx_compress_batch_res2` /
+  `cfx_decompress_batch_res2` - the predictor inside the codec's own launches, no scratch tensors; every other codec, and
+  log_compress_stats: `cfx_residual2_delta` / `cfx_residual2_update` around the codec; states in place either way); `simulate` ships the dequantised tensor (:117-119, :126-127); the fastpath accepts
   only BINARY / INT2 (:131, :277).
 
 Activations may be fp16 or bf16.  bf16 (what FLUX, CogVideoX, HunyuanVideo run in) is served by the 1-bit and 2-bit codecs - plus WARMUP and
@@ -334,9 +336,17 @@ def compact_compress(cache_key, x: torch.Tensor, compress_type: COMPACT_COMPRESS
                 _codec_decompress(cid, param, pkt, log_base, rec)
             _log(cache_key, log_base, None, x, rec, pkt)
         return pkt
-    # residual 2: second-order predictor - two native elementwise passes around the native codec, states updated in place
+    # residual 2: second-order predictor
     dbase = cache.get_delta_base(cache_key)
     assert dbase is not None, f"no second-order state for key {cache_key}: residual 2 needs two WARMUP steps"
+    if not cfg.log_compress_stats and codecs.res2_fused(cid, x, base, dbase):
+        # 1-bit / 2-bit: ONE fused call - the predictor inside the codec's own launches, both states updated in place on the arena
+        codecs.compress_batch_res2(cid, [x], [base], [dbase], [base], [dbase], [pkt], N, C, cfg.delta_decay_factor, param,
+                                   update_cache=update_cache)
+        if update_cache:
+            cache.put(cache_key, base, dbase)
+        return pkt
+    # every other codec (and log_compress_stats): two native elementwise passes around the native codec, states updated in place
     dd = _buf(cache_key, "dd", N * C, x).view(N, C)
     codecs.residual2_delta(x, base, dbase, dd)
     _codec_compress(cid, param, dd, None, None, pkt, update=False)
@@ -434,6 +444,16 @@ def _decompress(cache_key, compressed: torch.Tensor, compress_type: COMPACT_COMP
         return out.view(original_shape)
     dbase = cache.get_delta_base(cache_key)
     assert dbase is not None, f"no second-order state for key {cache_key}: residual 2 needs two WARMUP steps"
+    if not cfg.log_compress_stats and codecs.res2_fused(cid, base, dbase):
+        # 1-bit / 2-bit: ONE fused call (the reconstruction and, with update_cache, the decayed second-order state)
+        pk = compressed if compressed.data_ptr() % 16 == 0 else compressed.clone()
+        if update_cache:
+            codecs.decompress_batch_res2(cid, [pk], [base], [dbase], [base], [dbase], N, C, cfg.delta_decay_factor, param)
+            cache.put(cache_key, base, dbase)
+            return base.view(original_shape)
+        rec = torch.empty((N, C), dtype=base.dtype, device=compressed.device)
+        codecs.decompress_batch_res2(cid, [pk], [base], [dbase], [rec], [None], N, C, cfg.delta_decay_factor, param)
+        return rec.view(original_shape)
     recv = _buf(cache_key, "recv", N * C, base, base.dtype).view(N, C)
     _codec_decompress(cid, param, compressed, None, recv)
     if update_cache:
@@ -528,20 +548,26 @@ class _KVExchange:
         self.device = like.device
         self.tags = (tag_k, tag_v)
         self.xop = None              # the synchronous exchange as ONE native op per layer (xlayer.LayerOp)
-        self._xop_args = None
+        self._xop_args, self._xop_kw = None, {}
         self.steady = None           # (codec type, config, shape, generation, arena version, device) the bound op is valid for
 
-    def bind(self, sig, cid, param, N, C, n_half, shape, ef):
+    def bind(self, sig, cid, param, N, C, n_half, shape, ef, decay=None):
+        """decay != None: second-order residuals (compress_residual 2; 1-bit / 2-bit) - the layer op alone serves them"""
         def state(key):
             b = _cache.get_base(key)
             assert b is not None, f"no cached base for key {key}"
             return b
+
+        def state2(key):
+            d = _cache.get_delta_base(key)
+            assert d is not None, f"no second-order state for key {key}: residual 2 needs two WARMUP steps"
+            return d
         kb = [state(k) for k in self.kkeys]
         vb = [state(k) for k in self.vkeys]
         own = [kb[self.rank], vb[self.rank]]
         bases = [t for pair in zip(kb, vb) for t in pair]
         step = codecs.CFX_MAX_BATCH
-        for p in range(2):
+        for p in range(2 if decay is None else 0):      # (second order: no prepared first-order batches - the layer op below is the bound form)
             s_, r_, sl = self.send[p], self.recv[p], self.slot
             own_pkts = [s_[:n_half], s_[sl:sl + n_half]]
             pkts = [r_[i * sl:i * sl + n_half] for i in range(2 * self.world)]
@@ -574,11 +600,16 @@ class _KVExchange:
             peers = [(r, kb[r], vb[r]) for r in range(self.world) if r != self.rank]
             self._xop_args = (("gather",) + self.tags + (id(self.group) if self.group is not None else None,), cid, param, N, C,
                               self.rank, self.world, self.group, self.device, own, peers)
+            if decay is not None:
+                # the arena's delta_base buffers: stable once the second WARMUP step has stored them (cache.version is in `sig`)
+                self._xop_kw = dict(own_second=[state2(self.kkeys[self.rank]), state2(self.vkeys[self.rank])],
+                                    peer_second=[(state2(self.kkeys[r]), state2(self.vkeys[r])) for r, _, _ in peers], decay=decay)
+        assert decay is None or self._xop_args is not None
 
     def _drop_xop(self):
         if self.xop is not None:
             self.xop.close()
-        self.xop, self._xop_args, self.steady = None, None, None
+        self.xop, self._xop_args, self._xop_kw, self.steady = None, None, {}, None
 
     def step_steady(self, k, v):
         """`step` of the synchronous exchange with nothing to re-check: one native call."""
@@ -626,7 +657,7 @@ class _KVExchange:
             global _current_cache_key
             if self.xop is None:
                 from . import xlayer
-                self.xop = xlayer.LayerOp(*self._xop_args, own_update="ef")
+                self.xop = xlayer.LayerOp(*self._xop_args, own_update="ef", **self._xop_kw)
             with Profiler.scope("compact.exchange_layer"):
                 self.xop.run(k, v, self._stream())
             from ..collector import collector
@@ -679,11 +710,16 @@ def compact_all_gather_kv(tag_k, tag_v, k: torch.Tensor, v: torch.Tensor, comp_t
                 and _generation == st[3] and _cache.version == st[4] and k.device == st[5] and st[6] == _steady_flags(cfg, k)
                 and not cfg.log_compress_stats and k.is_contiguous() and v.is_contiguous()):
             return ex.step_steady(k, v)
-    fusable = (comp_type != T.WARMUP and not cfg.simulate_compress and cfg.compress_residual == 1
+    fusable = (comp_type != T.WARMUP and not cfg.simulate_compress and cfg.compress_residual in (1, 2)
                and not cfg.log_compress_stats and k.shape == v.shape and k.is_contiguous() and v.is_contiguous()
                and not _cache.quantize)
     if fusable:
         cid, param = _native(comp_type)
+    res2 = cfg.compress_residual == 2
+    if fusable and res2:
+        # second-order residuals: the 1-bit / 2-bit layer op serves them (synchronous exchange); everything else the general path
+        from . import xlayer
+        fusable = (not displaced and codecs.res2_fused(cid, k, v) and xlayer.usable(cid, dist.get_world_size(group), k.is_cuda))
     if not fusable:
         if displaced and comp_type != T.WARMUP:
             # never degrade silently to a synchronous gather: the displaced exchange exists for native first-order codecs only
@@ -704,11 +740,11 @@ def compact_all_gather_kv(tag_k, tag_v, k: torch.Tensor, v: torch.Tensor, comp_t
             ex.flush()
         ex = _kv_exchanges[xkey] = _KVExchange(tag_k, tag_v, rank, world, slot, k, group)
     ex.flush()
-    sig = (_generation, _cache.version, cid, param, N, C, tuple(k.shape), cfg.error_feedback)
+    sig = (_generation, _cache.version, cid, param, N, C, tuple(k.shape), cfg.error_feedback, cfg.compress_residual, cfg.delta_decay_factor)
     if ex.sig != sig:
-        ex.bind(sig, cid, param, N, C, n_half, k.shape, cfg.error_feedback)
+        ex.bind(sig, cid, param, N, C, n_half, k.shape, cfg.error_feedback, cfg.delta_decay_factor if res2 else None)
     out = ex.step(k, v, displaced)
-    if not displaced and ex.xop is not None and ex.pending is None and not cfg.simulate_compress and cfg.compress_residual == 1:
+    if not displaced and ex.xop is not None and ex.pending is None and not cfg.simulate_compress and cfg.compress_residual in (1, 2):
         ex.steady = (comp_type, cfg, k.shape, _generation, _cache.version, k.device, _steady_flags(cfg, k))
     elif displaced or ex.pending is not None:
         ex.steady = None             # a displaced delta is in flight: the next synchronous call takes the general path (which flushes it)

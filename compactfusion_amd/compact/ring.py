@@ -117,6 +117,8 @@ def _lane_has_chain(mod_idx, current_iter, group=None) -> bool:
         ctype = cfg.compress_func(mod_idx, current_iter if current_iter is not None else cm.compact_get_step())
     except Exception:  # noqa: BLE001  (a compress_func that needs arguments this call does not have: the forward itself will say so)
         return True
+    if cfg.compress_residual == 2 and ctype in (COMPACT_COMPRESS_TYPE.BINARY, COMPACT_COMPRESS_TYPE.INT2):
+        return False            # second-order residuals: the one layer op on the caller's stream (no lane chain for them)
     if ctype not in (COMPACT_COMPRESS_TYPE.LOW_RANK, COMPACT_COMPRESS_TYPE.LOW_RANK_Q):
         return True
     # (... and only while the steady layer is what will run: with the profiler's scopes or a live collector the general path takes the
@@ -481,8 +483,9 @@ class _LayerExchange:
         o = (2 * r + kv) * self.slot
         return self.recv[o:o + n_half]
 
-    def bind(self, sig, cid, param, N, C, n_half, kshape, vshape, ef):
-        """(Re)build the pointer tables against the current state arena."""
+    def bind(self, sig, cid, param, N, C, n_half, kshape, vshape, ef, decay=None):
+        """(Re)build the pointer tables against the current state arena.  decay != None: second-order residuals (compress_residual 2,
+        1-bit / 2-bit) - the layer op, with the arena's delta_base buffers, is the only bound form."""
         from .. import codecs
         cache = compact_cache()
 
@@ -490,9 +493,15 @@ class _LayerExchange:
             b = cache.get_base(key)
             assert b is not None, f"no cached base for key {key}: a WARMUP step must precede residual compression"
             return b
+
+        def state2(key):
+            d = cache.get_delta_base(key)
+            assert d is not None, f"no second-order state for key {key}: residual 2 needs two WARMUP steps"
+            return d
         own = [state(self.kkeys[self.rank]), state(self.vkeys[self.rank])]
         self._drop_xop()
-        if self._xop_wanted(cid, ef):
+        assert decay is None or self._xop_wanted(cid, ef, True)
+        if self._xop_wanted(cid, ef, decay is not None):
             # ONE native op per layer (xlayer.LayerOp): compress ; exchange ; reconstruct all peers - on the caller's stream, in front of
             # the local attention block.  The states are updated in place; the consumer reads them as the peers' K,V.
             from . import xlayer
@@ -503,8 +512,10 @@ class _LayerExchange:
                 bk, bv = state(self.kkeys[r]), state(self.vkeys[r])
                 peers.append((r, bk, bv))
                 self.peer_views.append((bk.view(kshape), bv.view(vshape)))
+            second = {} if decay is None else dict(own_second=[state2(self.kkeys[self.rank]), state2(self.vkeys[self.rank])],
+                                                   peer_second=[(state2(self.kkeys[r]), state2(self.vkeys[r])) for r in self.peers], decay=decay)
             self.xop = xlayer.LayerOp(("ring", self.kkeys[self.rank], id(self.group) if self.group is not None else None), cid, param, N, C,
-                                      self.rank, self.world, self.group, self.send.device, own, peers, own_update="ef" if ef else "x")
+                                      self.rank, self.world, self.group, self.send.device, own, peers, own_update="ef" if ef else "x", **second)
             self.comp, self.dec = None, []
             self.sig = sig
             return
@@ -545,7 +556,7 @@ class _LayerExchange:
             self.xop.close()
         self.xop = None
 
-    def _xop_wanted(self, cid, ef: bool = True) -> bool:
+    def _xop_wanted(self, cid, ef: bool = True, res2: bool = False) -> bool:
         """The layer's exchange as one native op on the caller's stream - unless the caller runs on the exchange lane's compute stream
         (then the chain runs beside the attention blocks on the CU-masked exchange stream) or asked for the lane (ring_exchange_stream="lane")."""
         from . import xlayer
@@ -555,8 +566,8 @@ class _LayerExchange:
             return False
         dev = self.send.device.index if self.send.device.index is not None else torch.cuda.current_device()
         # (the low-rank family has no chain of its own on the lane: on the compute stream too it takes the layer op, which leaves the peers'
-        # reconstructions to the exchange lane - xlayer.LayerOp.run(lane=True))
-        return xmode == "xlayer" or cid >= 100 or not lanes.on_compute_stream(dev)
+        # reconstructions to the exchange lane - xlayer.LayerOp.run(lane=True); nor have second-order residuals: the layer op wherever the caller is)
+        return xmode == "xlayer" or cid >= 100 or res2 or not lanes.on_compute_stream(dev)
 
     def close(self):
         """Release what the layer holds outside torch's allocator: native plans and (legacy CFX_RING_P2P chain) its IPC buffer + mappings."""
@@ -738,12 +749,21 @@ def _gather_schedule(q, k, v, ctype, mod_idx, rank, world, group, kkey, vkey, at
     N, C = cm._nc_shape(k.shape)
     warm = ctype == T.WARMUP
     native = (not warm) and (not cfg.simulate_compress) and cfg.compress_residual == 1
-    cid, param = cm._native(ctype) if native else (0, 0)
-    n_half = cm._packet_halves(cid, param, N, C) if native else \
+    # second-order residuals (1-bit / 2-bit, fp16): native where the layer op serves them - decided below, once the layer's exchange is known
+    res2 = (not warm) and (not cfg.simulate_compress) and cfg.compress_residual == 2
+    cid, param = cm._native(ctype) if (native or res2) else (0, 0)
+    n_half = cm._packet_halves(cid, param, N, C) if (native or res2) else \
         (N * C if (warm or cfg.simulate_compress) else cm._packet_halves(*cm._native(ctype), N, C))
     slot = (n_half + 127) // 128 * 128
     ex = _layer_exchange(mod_idx, rank, world, slot, k, group)
     send, recv, side = ex.send, ex.recv, ex.side
+    if res2:
+        from .. import codecs
+        res2 = (codecs.res2_fused(cid, k, v) and ex._xop_wanted(cid, True, True) and not cfg.log_compress_stats and v.shape == k.shape
+                and not compact_cache().quantize)
+        native = res2           # (not served by the layer op: the general path below, one call per tensor, as before)
+        if not native:
+            cid, param = 0, 0
     # steady state: K and V in ONE native compress sequence straight into the send slots, in-place EF state update
     # (the low-rank family - ids >= 100 - has the one-op form only: where that is not wanted, e.g. on the exchange lane, the general path below)
     fast = (native and (cid < 100 or ex._xop_wanted(cid, bool(cfg.error_feedback))) and not cfg.log_compress_stats and v.shape == k.shape
@@ -752,9 +772,9 @@ def _gather_schedule(q, k, v, ctype, mod_idx, rank, world, group, kkey, vkey, at
     sh = cur.cuda_stream if cur is not None else None
     if fast:
         cache = compact_cache()
-        sig = (cm._generation, cache.version, cid, param, N, C, tuple(kshape), cfg.error_feedback)
+        sig = (cm._generation, cache.version, cid, param, N, C, tuple(kshape), cfg.error_feedback, cfg.compress_residual, cfg.delta_decay_factor)
         if ex.sig != sig:
-            ex.bind(sig, cid, param, N, C, n_half, kshape, vshape, cfg.error_feedback)
+            ex.bind(sig, cid, param, N, C, n_half, kshape, vshape, cfg.error_feedback, cfg.delta_decay_factor if res2 else None)
         native_x = ex.plan is not None or ex.xop is not None
         with Profiler.scope("compact.compress_batch"):
             if native_x:

@@ -377,11 +377,16 @@ class LayerOp:
     own_update   "ef"     error feedback: own state <- own state + decode(own packet)   (ring.py: compact_compress(update_cache=True);
                           gather mode: the own shard is replaced by its reconstruction, main.py:406-419)
                  "x"      error feedback off in ring mode: own state <- the activation  (main.py:240-243)
+    own_second   second-order residuals (CompactConfig(residual=2); 1-bit / 2-bit, fp16, own_update "ef"): [K, V] delta_base buffers of
+    peer_second  this rank's shard, and [(K delta_base, V delta_base), ...] of the peers in the order of peer_states - with `decay`
+                 attached to the same op by cfx_plan_set_second_order (include/cfx.h, "Second-order residual"): both states of every
+                 tensor are updated in place, "ef" being the second-order update; compress ; exchange ; reconstruct in stream order
     """
 
     def __init__(self, key, cid: int, param: int, N: int, C: int, rank: int, world: int, group, device: torch.device,
                  own_states: Sequence[torch.Tensor], peer_states: Sequence[Tuple[int, torch.Tensor, torch.Tensor]],
-                 own_update: str = "ef"):
+                 own_update: str = "ef", own_second: Optional[Sequence[torch.Tensor]] = None,
+                 peer_second: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, decay: float = 0.0):
         assert own_update in ("ef", "x")
         assert 2 * len(peer_states) + 2 <= MAX_ITEMS, "a layer op carries at most CFX_MAX_BATCH reconstruction items"
         self.key, self.cid, self.param, self.N, self.C = key, int(cid), int(param), N, C
@@ -403,6 +408,13 @@ class LayerOp:
             raise NotImplementedError(f"torch.bfloat16 activations are not supported with codec id {self.cid} in the layer exchange op "
                                       "(bf16 runs with the 1-bit and 2-bit codecs)")
         self.cabi = self.cid if self.lowrank else codecs.codec_arg(self.cid, self.dtype)
+        self.own2 = None if own_second is None else list(own_second)
+        self.peer2 = [] if own_second is None else [tuple(p) for p in (peer_second or [])]
+        self.decay = float(decay)
+        if self.own2 is not None:
+            assert codecs.res2_fused(self.cid, *self.own, *self.own2, *[t for p in self.peer2 for t in p]) and own_update == "ef", \
+                "second-order states: the 1-bit and 2-bit codecs, fp16 GPU tensors, error feedback"
+            assert len(self.own2) == 2 and len(self.peer2) == len(self.peers), "one second-order state per own and per peer tensor"
         if self.lowrank:
             assert self.cid in (101, 102) and own_update == "ef", "the low-rank layer op exists with error feedback only"
             self.pkt_bytes = 2 * codecs.lr_packet_halves(self.quantized, N, C, self.param)
@@ -497,6 +509,15 @@ class LayerOp:
         nb = [o[0].data_ptr(), o[1].data_ptr()]
         return (_lib.CompItem * 2)(_lib.CompItem(None, o[0].data_ptr(), nb[0], pk_k), _lib.CompItem(None, o[1].data_ptr(), nb[1], pk_v))
 
+    def _second(self, plan, op: int, comp: bool, rec: bool) -> None:
+        """second-order states of plan op `op`: the own tensors' (its compress items) and / or the peers' (its reconstruction items)"""
+        if self.own2 is None:
+            return
+        c2 = (_lib.SecondItem * 2)(*[_lib.SecondItem(d.data_ptr(), d.data_ptr()) for d in self.own2]) if comp else None
+        ds = [d for p in self.peer2 for d in p] if rec else []
+        r2 = (_lib.SecondItem * len(ds))(*[_lib.SecondItem(d.data_ptr(), d.data_ptr()) for d in ds]) if ds else None
+        self._check(self.lib.cfx_plan_set_second_order(plan, op, 2 if comp else 0, c2, len(ds), r2, self.decay) == 0, "second-order states")
+
     def _build(self, sh: int):
         lib, ctx = self.lib, self.ctx
         cid, param, N, C = self.cabi, self.param, self.N, self.C
@@ -516,6 +537,7 @@ class LayerOp:
         if t == "none":
             c = (_lib.CompItem * 2)(*[_lib.CompItem(None, s.data_ptr(), s.data_ptr(), p.data_ptr()) for s, p in zip(self.own, self._solo_packets())])
             self._check(lib.cfx_plan_add_compress(plan, cid, N, C, param, self.flags, 2, c, wsp, wsn) == 0, "compress")
+            self._second(plan, 0, True, False)
         elif t == "p2p":
             reg = self.region
             for parity in (0, 1):
@@ -529,6 +551,7 @@ class LayerOp:
                 op = lib.cfx_plan_add_exchange_layer_p2p(plan, cid, N, C, param, self.flags, 2, c, n_rec, (_lib.DecompItem * n_rec)(*items),
                                                          reg.flag(None, parity), len(live), pf, wsp, wsn)
                 self._check(op == parity, "exchange layer (p2p)")
+                self._second(plan, op, True, True)
         elif t == "rccl":
             recv, slot = self._recv.data_ptr(), self.slot
             c = self._comp_items(recv + (2 * self.rank) * slot, recv + (2 * self.rank + 1) * slot)
@@ -539,6 +562,7 @@ class LayerOp:
             op = lib.cfx_plan_add_exchange_layer(plan, cid, N, C, param, self.flags, 2, c, n_rec, (_lib.DecompItem * n_rec)(*items),
                                                  self._comm.handle, recv + 2 * self.rank * slot, recv, 2 * slot, wsp, wsn)
             self._check(op == 0, "exchange layer (collective)")
+            self._second(plan, 0, True, True)
         else:
             send, recv, slot = self._send.data_ptr(), self._recv.data_ptr(), self.slot
             c = self._comp_items(send, send + slot)
@@ -548,6 +572,8 @@ class LayerOp:
                 items.append(_lib.DecompItem(recv + (2 * r) * slot, ks.data_ptr(), ks.data_ptr()))
                 items.append(_lib.DecompItem(recv + (2 * r + 1) * slot, vs.data_ptr(), vs.data_ptr()))
             self._check(lib.cfx_plan_add_decompress(plan, cid, N, C, param, n_rec, (_lib.DecompItem * n_rec)(*items)) == 1, "reconstruct")
+            self._second(plan, 0, True, False)
+            self._second(plan, 1, False, True)
         self._check(lib.cfx_plan_finalize(plan) == 0, "finalize")
         ent = self._plans[sh] = (plan, keep)
         return ent
@@ -779,6 +805,14 @@ class LayerOp:
         for r, ks, vs in self.peers:
             ks.view(torch.int32).reshape(-1).copy_(every[r, 0])
             vs.view(torch.int32).reshape(-1).copy_(every[r, 1])
+        if self.own2 is not None:
+            # second order: the owners' delta_base too (as it was before the failed execution: behind the first-order states in `snap`)
+            d0 = snap[2 + 2 * len(self.peers):][:2] if len(snap) > 2 + 2 * len(self.peers) else self.own2
+            own = torch.cat([d0[0].reshape(-1).view(torch.int32), d0[1].reshape(-1).view(torch.int32)])
+            dist.all_gather_into_tensor(every.view(-1), own, group=self.group)
+            for (r, _, _), (kd, vd) in zip(self.peers, self.peer2):
+                kd.view(torch.int32).reshape(-1).copy_(every[r, 0])
+                vd.view(torch.int32).reshape(-1).copy_(every[r, 1])
 
     def _run_validated(self, k, v, sh) -> None:
         """A validated p2p execution of this layer: run it, then check that no gate timed out and that what this rank reconstructed for
@@ -788,6 +822,8 @@ class LayerOp:
         from their owners, the group's arena is marked bad and the execution is repeated on the next transport."""
         reg, lib, ctx = self.region, self.lib, self.ctx
         states = list(self.own) + [t for _, ks, vs in self.peers for t in (ks, vs)]
+        if self.own2 is not None:              # (restored with the rest on a failure; _resync fetches the owners' copies of both states)
+            states += list(self.own2) + [d for p in self.peer2 for d in p]
         snap = [t.clone() for t in states]
         ent = self._plans[sh]
         op = reg.n_exec & 1
@@ -805,11 +841,13 @@ class LayerOp:
             lib.cfx_gate_recover(ctx)          # local counters only: the launches that follow must not sit out the timeout on a short count
         if self.own_update == "ef":
             # error feedback: what every peer reconstructed of a shard IS its owner's state
-            mine = self._checksums(self.own)
-            allc = torch.empty(self.world * 2, dtype=torch.int64, device=self.device)
+            # (second order: of both states)
+            mine = self._checksums(self.own + (self.own2 or []))
+            n = mine.numel()
+            allc = torch.empty(self.world * n, dtype=torch.int64, device=self.device)
             dist.all_gather_into_tensor(allc, mine, group=self.group)
-            for r, ks, vs in self.peers:
-                if not torch.equal(self._checksums([ks, vs]), allc[2 * r:2 * r + 2]):
+            for i, (r, ks, vs) in enumerate(self.peers):
+                if not torch.equal(self._checksums([ks, vs] + (list(self.peer2[i]) if self.own2 is not None else [])), allc[n * r:n * r + n]):
                     bad = 1
         else:
             # without error feedback the owner keeps the activation and only its peers hold previous copy + decoded packet (main.py:233):

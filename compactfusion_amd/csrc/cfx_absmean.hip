@@ -41,7 +41,8 @@ extern "C" CFX_HIDDEN void cfx_i_lr_factor_offsets(int N, int C, int rank, size_
 template <bool EMIT_BITS, int US, bool WT = false, int NW = WAVES, bool PUB = false, bool KEEP = false, bool TAG = false, class E = ElemF16>
 __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int N, int C, int R, int CB, int bx, int by,
                                                    u64* rowpart, u64 (*sm)[TILE_C], Probe probe = Probe(),
-                                                   h16x8* xk = nullptr, h16x8* bk = nullptr, TagArena ta = TagArena()) {
+                                                   h16x8* xk = nullptr, h16x8* bk = nullptr, TagArena ta = TagArena(),
+                                                   const h16* dbase = nullptr) {
 #define SSTAMP(k) probe.at(k)
     const TileCoord t = tile_coord_at(bx, by, N, C, R);
     const int cb = bx;
@@ -59,7 +60,7 @@ __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int 
     for (int i = 0; i < 8; ++i) col[i] = 0.0;
 
     for (int r = t.r0 + t.w; r < t.r1; r += NW * US) {
-        h16x8 xv[US], bv[US];
+        h16x8 xv[US], bv[US], dv[E::second ? US : 1] = {};      // (dv: second order only - the statistics tile loop's one extra load)
 #pragma unroll
         for (int j = 0; j < US; ++j) {
             const int rr = r + NW * j;
@@ -69,6 +70,7 @@ __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int 
                 // 1-bit: x is not needed again (the EF pass works from the packed bits) -> streaming load
                 xv[j] = EMIT_BITS ? ld8nt(x + (size_t)rr * C + t.c) : ld8(x + (size_t)rr * C + t.c);
                 if (base) bv[j] = ld8(base + (size_t)rr * C + t.c);
+                if constexpr (E::second) dv[j] = ld8(dbase + (size_t)rr * C + t.c);
             }
         }
         if (KEEP) {
@@ -81,7 +83,7 @@ __device__ __forceinline__ void absmean_stats_body(const cfx_comp_item& it, int 
         for (int j = 0; j < US; ++j) {
             const int rr = r + NW * j;
             if (rr < t.r1 && t.act) {
-                const h16x8 d = el_diff<E>(xv[j], bv[j]);
+                const h16x8 d = el_diff<E>(xv[j], bv[j], dv[E::second ? j : 0]);
                 const h16x8 a = habs8(d);
                 unsigned byte = 0;
                 double rsum = 0.0;
@@ -153,6 +155,13 @@ template <bool EMIT_BITS, class E>
 __global__ __launch_bounds__(NTHR) void k_absmean_stats(BatchC batch, int N, int C, int R, u64* ws, size_t ws_stride) {
     __shared__ u64 sm[WAVES][TILE_C];
     absmean_stats_body<EMIT_BITS, UNROLL_S, false, WAVES, false, false, false, E>(batch.it[blockIdx.z], N, C, R, gridDim.x, blockIdx.x, blockIdx.y, ws + (size_t)blockIdx.z * ws_stride, sm);
+}
+// second order: the same body over dd = (x - base) - delta_base (Pred2; a kernel of its own name - its batch carries the extra operands)
+template <bool EMIT_BITS>
+__global__ __launch_bounds__(NTHR) void k_absmean_stats2(BatchC2 batch, int N, int C, int R, u64* ws, size_t ws_stride) {
+    __shared__ u64 sm[WAVES][TILE_C];
+    absmean_stats_body<EMIT_BITS, UNROLL_S, false, WAVES, false, false, false, Pred2>(batch.it[blockIdx.z], N, C, R, gridDim.x, blockIdx.x, blockIdx.y, ws + (size_t)blockIdx.z * ws_stride, sm,
+                                                                                  Probe(), nullptr, nullptr, TagArena(), (const h16*)batch.s2[blockIdx.z].delta_base);
 }
 
 // finalize: U[n] = rowmean/mean(rowmean) (1-bit, fastpath.py:164-165) or rowmean/(mean+1e-6) (2-bit, :619-622);
@@ -241,7 +250,8 @@ __global__ __launch_bounds__(1024) void k_absmean_finalize(BatchC batch, int N, 
 // ---------------------------------------------------------------------------------------------------
 // UN = rows a wave keeps in flight (2 on the whole chip; 4 on a CU-masked lane, where bytes in flight per CU bound the rate)
 template <int NW = WAVES, int UN = UNROLL, class E = ElemF16>
-__device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, int N, int C, int R, int tile_x, int tile_y) {
+__device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, int N, int C, int R, int tile_x, int tile_y,
+                                                    const h16* dbase = nullptr, h16* ndelta = nullptr, float decay = 0.f) {
     const TileCoord t = tile_coord_at(tile_x, tile_y, N, C, R);
     const unsigned char* pk = (const unsigned char*)it.packet;
     const int C8 = C >> 3;
@@ -254,7 +264,7 @@ __device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, i
     if (t.act) v8 = ld8_tail(V + t.c, val16);
 
     for (int r = t.r0 + t.w; r < t.r1; r += NW * UN) {
-        h16x8 bv[UN];
+        h16x8 bv[UN], dv[E::second ? UN : 1] = {};
         unsigned by[UN];
         h16 u[UN];
 #pragma unroll
@@ -265,6 +275,7 @@ __device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, i
             u[j] = (h16)0;
             if (rr < t.r1 && t.act) {
                 if (base) bv[j] = ld8nt(base + (size_t)rr * C + t.c);
+                if constexpr (E::second) dv[j] = ld8nt(dbase + (size_t)rr * C + t.c);
                 by[j] = pk[(size_t)rr * C8 + (t.c >> 3)];
                 u[j] = U[rr];
             }
@@ -278,7 +289,8 @@ __device__ __forceinline__ void binary_dequant_body(const cfx_decomp_item& it, i
 #pragma unroll
                 for (int i = 0; i < 8; ++i) sb[i] ^= ((by[j] >> i) & 1u) ? (u16)0 : (u16)0x8000;   // (2b-1)*s
                 const h16x8 recv = __builtin_bit_cast(h16x8, sb);
-                st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bv[j], recv));
+                if constexpr (E::second) el_state2_store(out + (size_t)rr * C + t.c, ndelta ? ndelta + (size_t)rr * C + t.c : nullptr, bv[j], dv[j], recv, decay);
+                else st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bv[j], recv));
             }
         }
     }
@@ -289,6 +301,13 @@ __global__ __launch_bounds__(NTHR) void k_binary_dequant(BatchD batch, int N, in
     // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
     if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
     binary_dequant_body<WAVES, UN, E>(batch.it[blockIdx.z], N, C, R, blockIdx.x, blockIdx.y);
+}
+// second order: both states from the packet (the receiver's reconstruction, and the sender's update from its own packet)
+template <int UN>
+__global__ __launch_bounds__(NTHR) void k_binary_dequant2(BatchD2 batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
+    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
+    binary_dequant_body<WAVES, UN, Pred2>(batch.it[blockIdx.z], N, C, R, blockIdx.x, blockIdx.y, (const h16*)batch.s2[blockIdx.z].delta_base,
+                                          (h16*)batch.s2[blockIdx.z].new_delta_base, batch.decay);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -972,7 +991,7 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
                                                    u64* rowpart, unsigned* tick, int per_byte, int eps_mode, u64 (*sm)[TILE_C], int dbg,
                                                    Probe probe, unsigned* gate = nullptr, unsigned gate_expect = 0, int flags = 0,
                                                    unsigned* gate2 = nullptr, unsigned expect2 = 0, unsigned* err = nullptr, long long timeout = 0,
-                                                   TagArena ta = TagArena(), int sv = 1) {
+                                                   TagArena ta = TagArena(), int sv = 1, const h16* dbase = nullptr) {
     // developer probes (cfx_dev.h): per-workgroup phase times, 100 MHz wall clock
 #define STAMP(k) probe.at(k)
     STAMP(0);
@@ -997,7 +1016,7 @@ __device__ __forceinline__ void absmean_fused_body(const cfx_comp_item& it, int 
     }
 #endif
     h16x8 xk[KEEP ? US : 1], bk[KEEP ? US : 1];
-    absmean_stats_body<EMIT_BITS, US, true, FUSED_NW, GATED, KEEP, GATED, E>(it, N, C, R, CB, bx, by, rowpart, sm, probe, xk, bk, ta);
+    absmean_stats_body<EMIT_BITS, US, true, FUSED_NW, GATED, KEEP, GATED, E>(it, N, C, R, CB, bx, by, rowpart, sm, probe, xk, bk, ta, dbase);
     STAMP(1);
     if constexpr (GATED) {
         // the layer launches: tagged partials, fixed reducers (absmean_tagged_jobs) - nothing to drain, no ticket to draw
@@ -1154,6 +1173,21 @@ __global__ __launch_bounds__(FUSED_NT, GATE_WPE) __attribute__((amdgpu_num_vgpr(
     }
 }
 
+// second order: the statistics group alone (no ride-along, no gated items: a second-order layer runs compress ; exchange ; reconstruct in
+// stream order) over dd = (x - base) - delta_base - absmean_fused_body with Pred2, the in-launch finalize as it is
+template <bool EMIT_BITS, int US>
+__global__ __launch_bounds__(FUSED_NT, GATE_WPE) void k_absmean_compress2(BatchC2 batch, FusedArgs a) {
+    __shared__ u64 sm[FUSED_NW][TILE_C];
+    const int b = blockIdx.x;
+    const int per = a.CB * a.P;
+    const int z = b / per, rem = b - z * per;
+    const int by = rem / a.CB;
+    absmean_fused_body<EMIT_BITS, US, false, false, Pred2>(batch.it[z], a.N, a.C, a.R, a.CB, a.P, rem - by * a.CB, by, a.ws + (size_t)z * a.ws_stride,
+                                                           a.tick + z * TICK_WORDS, a.per_byte, a.eps_mode, sm, a.dbg,
+                                                           a.probe.of(b), a.gate, a.gate_expect, 0, nullptr, 0u, a.gate_err, a.timeout,
+                                                           TagArena(), 1, (const h16*)batch.s2[z].delta_base);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Software-pipelined 1-bit exchange step: ONE launch carries three independent groups of workgroups,
 //   finalize(layer j+1)  |  stats + sign bits(layer j+2)  |  dequant + add(layer j)
@@ -1207,8 +1241,8 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // ---------------------------------------------------------------------------------------------------
 
 template <class E>
-__global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C, int R, int flags) {
-    const cfx_comp_item it = batch.it[blockIdx.z];
+__device__ __forceinline__ void int2_quant_body(const cfx_comp_item it, int N, int C, int R, int flags,
+                                                const h16* dbase = nullptr, h16* ndelta = nullptr, float decay = 0.f) {
     const TileCoord t = tile_coord(N, C, R);
     const int C4 = C >> 2;
     unsigned char* pk = (unsigned char*)it.packet;
@@ -1224,7 +1258,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
     if (t.act) ch8 = ld8_tail(CH + t.c, al16);
 
     for (int r = t.r0 + t.w; r < t.r1; r += WAVES * UNROLL) {
-        h16x8 xv[UNROLL], bv[UNROLL];
+        h16x8 xv[UNROLL], bv[UNROLL], dv[E::second ? UNROLL : 1] = {};
         h16 tk[UNROLL];
 #pragma unroll
         for (int j = 0; j < UNROLL; ++j) {
@@ -1233,6 +1267,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
             if (rr < t.r1 && t.act) {
                 xv[j] = ld8nt(x + (size_t)rr * C + t.c);
                 if (base) bv[j] = ld8nt(base + (size_t)rr * C + t.c);
+                if constexpr (E::second) dv[j] = ld8nt(dbase + (size_t)rr * C + t.c);
                 tk[j] = TOK[rr];
             }
         }
@@ -1240,7 +1275,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
         for (int j = 0; j < UNROLL; ++j) {
             const int rr = r + WAVES * j;
             if (rr < t.r1 && t.act) {
-                const h16x8 d = el_diff<E>(xv[j], bv[j]);
+                const h16x8 d = el_diff<E>(xv[j], bv[j], dv[E::second ? j : 0]);
                 const h16x8 thr = ch8 * tk[j];                                   // fastpath.py:536
                 const h16x8 a = habs8(d);
                 unsigned code = 0;
@@ -1251,7 +1286,10 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
                     code |= ((s << 1) | m) << (2 * i);
                 }
                 *reinterpret_cast<u16*>(pk + (size_t)rr * C4 + (t.c >> 2)) = (u16)code;
-                if (upd) {
+                if constexpr (E::second) {
+                    // (error feedback is what the second-order update IS: CFX_FLAG_NO_EF never reaches this form)
+                    if (upd) el_state2_store(nb + (size_t)rr * C + t.c, ndelta + (size_t)rr * C + t.c, bv[j], dv[j], int2_recv((u16)code, thr), decay);
+                } else if (upd) {
                     h16x8 o;
                     if (ef) {
                         const h16x8 recv = int2_recv((u16)code, thr);
@@ -1267,13 +1305,20 @@ __global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C,
         }
     }
 }
+template <class E>
+__global__ __launch_bounds__(NTHR) void k_int2_quant(BatchC batch, int N, int C, int R, int flags) {
+    int2_quant_body<E>(batch.it[blockIdx.z], N, C, R, flags);
+}
+// second order: codes of dd = (x - base) - delta_base, both states from them
+__global__ __launch_bounds__(NTHR) void k_int2_quant2(BatchC2 batch, int N, int C, int R, int flags) {
+    int2_quant_body<Pred2>(batch.it[blockIdx.z], N, C, R, flags, (const h16*)batch.s2[blockIdx.z].delta_base,
+                           (h16*)batch.s2[blockIdx.z].new_delta_base, batch.decay);
+}
 
 // 2-bit dequant + base add        replaces _int2_dequant_fastpath (fastpath.py:672-741)
 template <class E>
-__global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
-    // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
-    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
-    const cfx_decomp_item it = batch.it[blockIdx.z];
+__device__ __forceinline__ void int2_dequant_body(const cfx_decomp_item it, int N, int C, int R,
+                                                  const h16* dbase = nullptr, h16* ndelta = nullptr, float decay = 0.f) {
     const TileCoord t = tile_coord(N, C, R);
     const int C4 = C >> 2;
     const unsigned char* pk = (const unsigned char*)it.packet;
@@ -1286,7 +1331,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int 
     if (t.act) ch8 = ld8_tail(CH + t.c, al16);
 
     for (int r = t.r0 + t.w; r < t.r1; r += WAVES * UNROLL) {
-        h16x8 bv[UNROLL];
+        h16x8 bv[UNROLL], dv[E::second ? UNROLL : 1] = {};
         u16 cd[UNROLL];
         h16 tk[UNROLL];
 #pragma unroll
@@ -1295,6 +1340,7 @@ __global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int 
             bv[j] = (h16x8)(h16)0; cd[j] = 0; tk[j] = (h16)0;
             if (rr < t.r1 && t.act) {
                 if (base) bv[j] = ld8nt(base + (size_t)rr * C + t.c);
+                if constexpr (E::second) dv[j] = ld8nt(dbase + (size_t)rr * C + t.c);
                 cd[j] = *reinterpret_cast<const u16*>(pk + (size_t)rr * C4 + (t.c >> 2));
                 tk[j] = TOK[rr];
             }
@@ -1305,10 +1351,22 @@ __global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int 
             if (rr < t.r1 && t.act) {
                 const h16x8 thr = ch8 * tk[j];
                 const h16x8 recv = int2_recv(cd[j], thr);
-                st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bv[j], recv));
+                if constexpr (E::second) el_state2_store(out + (size_t)rr * C + t.c, ndelta ? ndelta + (size_t)rr * C + t.c : nullptr, bv[j], dv[j], recv, decay);
+                else st8nt(out + (size_t)rr * C + t.c, el_state<E>(base != nullptr, bv[j], recv));
             }
         }
     }
+}
+template <class E>
+__global__ __launch_bounds__(NTHR) void k_int2_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
+    // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
+    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
+    int2_dequant_body<E>(batch.it[blockIdx.z], N, C, R);
+}
+__global__ __launch_bounds__(NTHR) void k_int2_dequant2(BatchD2 batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
+    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
+    int2_dequant_body<Pred2>(batch.it[blockIdx.z], N, C, R, (const h16*)batch.s2[blockIdx.z].delta_base,
+                             (h16*)batch.s2[blockIdx.z].new_delta_base, batch.decay);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1533,7 +1591,64 @@ static unsigned scale_jobs_arrivals(int C, int sv, int batch) {
     return (unsigned)batch * (unsigned)((C + cw - 1) / cw + 1);
 }
 
+// Second-order compress (cfx_compress_batch_res2; include/cfx.h, "Second-order residual"): the sequence of a plain compress call - statistics
+// with the in-launch finalize, or statistics ; finalize - over dd = (x - base) - delta_base, then the codes (2-bit) and, with
+// CFX_FLAG_UPDATE_CACHE, both states from the call's own packet: the launches of the first-order call, instantiated for Pred2, under
+// their first-order twins' kernel ids.  No layer form: compress_impl refuses ride-along and gated items beside second-order states.
+static int absmean_compress2(CompressCall& cc) {
+    cfx_ctx* ctx = cc.ctx;
+    const int codec = cc.codec, N = cc.N, C = cc.C, batch = cc.batch, CB = cc.CB, R = cc.R, P = cc.P;
+    hipStream_t s = (hipStream_t)cc.stream;
+    BatchC2 b;
+    memset(&b, 0, sizeof(b));
+    for (int i = 0; i < batch; ++i) { b.it[i] = cc.b.it[i]; b.s2[i] = cc.second[i]; }
+    b.decay = cc.decay;
+    const int Rq = auto_rows(ctx, N, C, batch, true);
+    const dim3 gridq(CB, (N + Rq - 1) / Rq, batch);
+    const int per_byte = codec == CFX_CODEC_BINARY ? 8 : 4;
+    if (cc.fused) {
+        FusedArgs a;
+        memset(&a, 0, sizeof(a));
+        a.N = N; a.C = C; a.CB = CB; a.R = R; a.P = P;
+        a.n_st = CB * P * batch;
+        a.per_byte = per_byte; a.eps_mode = codec == CFX_CODEC_INT2 ? 1 : 0;
+        a.ws = cc.ws; a.ws_stride = cc.wstride; a.tick = cc.tick;
+        a.probe = cfx_i_probe(ctx);
+        a.gate_err = ctx->gate_err;
+        a.timeout = ctx->gate_timeout;
+        const dim3 g(a.n_st);
+        if (codec == CFX_CODEC_BINARY) {
+            if (R % 32 == 0) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_BITS, s, (k_absmean_compress2<true, 4>), g, dim3(FUSED_NT), 0, s, b, a);
+            else LAUNCH(ctx, KID_ABSMEAN_COMPRESS_BITS, s, (k_absmean_compress2<true, 2>), g, dim3(FUSED_NT), 0, s, b, a);
+        } else {
+            if (R % 32 == 0) LAUNCH(ctx, KID_ABSMEAN_COMPRESS, s, (k_absmean_compress2<false, 4>), g, dim3(FUSED_NT), 0, s, b, a);
+            else LAUNCH(ctx, KID_ABSMEAN_COMPRESS, s, (k_absmean_compress2<false, 2>), g, dim3(FUSED_NT), 0, s, b, a);
+        }
+    } else {
+        const dim3 grid(CB, P, batch);
+        if (codec == CFX_CODEC_BINARY) LAUNCH(ctx, KID_ABSMEAN_STATS_BITS, s, (k_absmean_stats2<true>), grid, dim3(NTHR), 0, s, b, N, C, R, cc.ws, cc.wstride);
+        else LAUNCH(ctx, KID_ABSMEAN_STATS, s, (k_absmean_stats2<false>), grid, dim3(NTHR), 0, s, b, N, C, R, cc.ws, cc.wstride);
+        LAUNCH(ctx, KID_ABSMEAN_FINALIZE, s, k_absmean_finalize, dim3(1 + (C + 255) / 256, batch), dim3(1024), 0, s, cc.b, N, C, CB, P, per_byte,
+               codec == CFX_CODEC_INT2 ? 1 : 0, (const u64*)cc.ws, cc.wstride);
+    }
+    if (codec == CFX_CODEC_INT2) {
+        LAUNCH(ctx, KID_INT2_QUANT, s, k_int2_quant2, gridq, dim3(NTHR), 0, s, b, N, C, Rq, cc.flags);
+    } else if (cc.upd) {
+        // the sender's update == the receiver's reconstruction of our own packet onto our own two states
+        BatchD2 d;
+        memset(&d, 0, sizeof(d));
+        for (int i = 0; i < batch; ++i) {
+            d.it[i].packet = b.it[i].packet; d.it[i].base = b.it[i].base; d.it[i].recon = b.it[i].new_base;
+            d.s2[i] = b.s2[i];
+        }
+        d.decay = cc.decay;
+        LAUNCH(ctx, KID_BINARY_EF, s, (k_binary_dequant2<UNROLL>), gridq, dim3(NTHR), 0, s, d, N, C, Rq, (unsigned*)nullptr, 0u);
+    }
+    return check_launch(ctx, "second-order compress launch");
+}
+
 int cfx_i_absmean_compress(CompressCall& cc) {
+    if (cc.second) return absmean_compress2(cc);
     cfx_ctx* ctx = cc.ctx;
     const int codec = cc.codec, N = cc.N, C = cc.C, param = cc.param, flags = cc.flags, batch = cc.batch, n_ride = cc.n_ride, CB = cc.CB;
     int n_gated = cc.n_gated;
@@ -1755,6 +1870,19 @@ int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, bool bf16, int N, int C, i
         } else LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<UNROLL, EL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
     } else LAUNCH_EL(bf16, ctx, KID_INT2_DEQUANT, s, (k_int2_dequant<EL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
     return check_launch(ctx, "decompress launch");
+}
+
+// second order: the reconstruction launches of cfx_i_absmean_decompress, instantiated for Pred2 (same tile maps, same kernel ids)
+int cfx_i_absmean_decompress2(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD2& b, int R, void* stream, unsigned* pre, unsigned pre_val) {
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, batch);
+    if (codec == CFX_CODEC_BINARY) {
+        if (stream_cu_count(ctx, stream) < 128) {
+            const int R4 = WAVES * 4;
+            LAUNCH(ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant2<4>), dim3(grid.x, (N + R4 - 1) / R4, batch), dim3(NTHR), 0, s, b, N, C, R4, pre, pre_val);
+        } else LAUNCH(ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant2<UNROLL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+    } else LAUNCH(ctx, KID_INT2_DEQUANT, s, k_int2_dequant2, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+    return check_launch(ctx, "second-order decompress launch");
 }
 
 extern "C" {

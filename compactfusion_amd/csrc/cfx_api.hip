@@ -515,6 +515,35 @@ int cfx_decompress_batch(cfx_ctx* ctx, int codec, int N, int C, int param, int b
     return cfx_i_decompress_checked(ctx, codec, N, C, param, batch, items, stream, nullptr, 0u);
 }
 
+// second order (include/cfx.h, "Second-order residual"): cfx_i_decompress_checked's checks in its order, then the second-order launch
+int cfx_i_decompress2_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int param, int batch, const cfx_decomp_item* items,
+                              const cfx_second_item* second, float decay, void* stream, unsigned* pre, unsigned pre_val) {
+    bool bf16 = false;
+    const int codec = codec_id(codec_arg, &bf16);
+    if (!ctx || !items || !second) return fail(ctx, CFX_ERR_NULL, "decompress: null ctx/items/second");
+    if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "decompress: batch out of range");
+    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec >= 1 && codec <= 5 ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
+    if ((codec != CFX_CODEC_BINARY && codec != CFX_CODEC_INT2) || bf16)
+        return fail(ctx, CFX_ERR_CODEC, "decompress: second-order states need the 1-bit or 2-bit codec, fp16");
+    BatchD2 b;
+    memset(&b, 0, sizeof(b));
+    for (int i = 0; i < batch; ++i) {
+        if (!items[i].packet || !items[i].recon) return fail(ctx, CFX_ERR_NULL, "decompress: null packet/recon");
+        if (!items[i].base || !second[i].delta_base) return fail(ctx, CFX_ERR_NULL, "decompress: second-order states need base and delta_base");
+        if (!AL16(items[i].packet) || !AL16(items[i].recon) || !AL16(items[i].base) || !AL16(second[i].delta_base) || !AL16(second[i].new_delta_base))
+            return fail(ctx, CFX_ERR_ALIGN, "decompress: pointers must be 16-byte aligned");
+        b.it[i] = items[i];
+        b.s2[i] = second[i];
+    }
+    b.decay = decay;
+    return cfx_i_absmean_decompress2(ctx, codec, N, C, batch, b, auto_rows(ctx, N, C, batch, false), stream, pre, pre_val);
+}
+
+int cfx_decompress_batch_res2(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items,
+                              const cfx_second_item* second, float decay, void* stream) {
+    return cfx_i_decompress2_checked(ctx, codec, N, C, param, batch, items, second, decay, stream, nullptr, 0u);
+}
+
 int cfx_i_fused_rows(const cfx_ctx* ctx, int N, int C, int batch, int cus) {
     if (ctx->stats_rows > 0) return (ctx->stats_rows + 15) & ~15;
     // 8 waves x 4 rows in flight = 32 rows per wave step; taller tiles (fewer partials per column for the last arriver to
@@ -573,7 +602,8 @@ void cfx_i_fill_p2p(cfx_ctx* ctx, CfxXGate* xg, P2PInline& p) {
 
 static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
                          int n_ride, const cfx_decomp_item* ride, int n_gated, const cfx_decomp_item* gated,
-                         void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg = nullptr) {
+                         void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg = nullptr,
+                         const cfx_second_item* second = nullptr, float decay = 0.f) {
     bool bf16 = false;
     const int codec = codec_id(codec_arg, &bf16);      // (0: no such codec - the shape check below says so)
     if (xg) { xg->taken = 0; xg->inline_done = 0; xg->p_gate = xg->f_gate = nullptr; xg->p_expect = xg->f_expect = 0; xg->p_count = 1; }
@@ -583,13 +613,20 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     if (!shape_ok(codec, N, C, param)) return fail(ctx, codec >= 1 && codec <= 5 ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "compress: bad codec/shape");
     if (n_ride < 0 || n_ride > CFX_MAX_BATCH || (n_ride && !ride)) return fail(ctx, CFX_ERR_BATCH, "compress: ride-along batch out of range");
     if (n_ride && codec != CFX_CODEC_BINARY) return fail(ctx, CFX_ERR_CODEC, "compress: ride-along reconstruction items need the 1-bit codec");
+    // second-order states (include/cfx.h, "Second-order residual"): the 1-bit and 2-bit codecs, fp16, error feedback on, no layer form
+    if (second && ((codec != CFX_CODEC_BINARY && codec != CFX_CODEC_INT2) || bf16 || (flags & CFX_FLAG_NO_EF) || n_ride || n_gated || xg))
+        return fail(ctx, CFX_ERR_CODEC, "compress: second-order states need the 1-bit or 2-bit codec, fp16, no CFX_FLAG_NO_EF, no ride-along / gated items");
     const bool upd = flags & CFX_FLAG_UPDATE_CACHE;
     BatchC b;
     memset(&b, 0, sizeof(b));
     for (int i = 0; i < batch; ++i) {
         if (!items[i].x || !items[i].packet) return fail(ctx, CFX_ERR_NULL, "compress: null x/packet");
         if (upd && !items[i].new_base) return fail(ctx, CFX_ERR_NULL, "compress: UPDATE_CACHE needs new_base");
+        if (second && (!items[i].base || !second[i].delta_base)) return fail(ctx, CFX_ERR_NULL, "compress: second-order states need base and delta_base");
+        if (second && upd && !second[i].new_delta_base) return fail(ctx, CFX_ERR_NULL, "compress: UPDATE_CACHE needs new_delta_base");
         if (!AL16(items[i].x) || !AL16(items[i].base) || !AL16(items[i].new_base) || !AL16(items[i].packet))
+            return fail(ctx, CFX_ERR_ALIGN, "compress: pointers must be 16-byte aligned");
+        if (second && (!AL16(second[i].delta_base) || !AL16(second[i].new_delta_base)))
             return fail(ctx, CFX_ERR_ALIGN, "compress: pointers must be 16-byte aligned");
         b.it[i] = items[i];
     }
@@ -632,6 +669,7 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     cc.n_ride = n_ride; cc.n_gated = n_gated; cc.gated = gated; cc.stream = stream; cc.xg = xg; cc.b = b; cc.rd = rd; cc.gd = gd;
     cc.ws = ws; cc.wstride = wstride; cc.CB = CB; cc.upd = upd; cc.capturing = capturing; cc.bf16 = bf16;
     cc.fused = false; cc.tick = nullptr; cc.slot = 0; cc.stream_cus = 0; cc.R = cc.P = 0;
+    cc.second = second; cc.decay = decay;
     if (codec == CFX_CODEC_TOPK) return cfx_i_topk_compress(cc);
 
     // statistics + finalize: ONE launch with the in-launch finalize (default), or the two-kernel sequence
@@ -664,6 +702,12 @@ int cfx_compress_batch_gated(cfx_ctx* ctx, int codec, int N, int C, int param, i
                              int n_ride, const cfx_decomp_item* ride, int n_gated, const cfx_decomp_item* gated,
                              void* workspace, size_t workspace_bytes, void* stream) {
     return compress_impl(ctx, codec, N, C, param, flags, batch, items, n_ride, ride, n_gated, gated, workspace, workspace_bytes, stream);
+}
+
+int cfx_compress_batch_res2(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
+                            const cfx_second_item* second, float decay, void* workspace, size_t workspace_bytes, void* stream) {
+    if (ctx && items && !second) return fail(ctx, CFX_ERR_NULL, "compress: null second-order states");
+    return compress_impl(ctx, codec, N, C, param, flags, batch, items, 0, nullptr, 0, nullptr, workspace, workspace_bytes, stream, nullptr, second, decay);
 }
 
 int cfx_gate_errors(cfx_ctx* ctx) {
@@ -740,8 +784,12 @@ size_t cfx_i_ws_words(int codec, int N, int C) { return ws_words(codec, N, C); }
 int cfx_i_stream_cus(cfx_ctx* ctx, void* stream) { return stream_cu_count_impl(ctx, stream); }
 int cfx_i_compress_impl(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
                         int n_ride, const cfx_decomp_item* ride, int n_gated, const cfx_decomp_item* gated,
-                        void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg) {
-    return compress_impl(ctx, codec, N, C, param, flags, batch, items, n_ride, ride, n_gated, gated, workspace, workspace_bytes, stream, xg);
+                        void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg, const cfx_second_item* second, float decay) {
+    return compress_impl(ctx, codec, N, C, param, flags, batch, items, n_ride, ride, n_gated, gated, workspace, workspace_bytes, stream, xg, second, decay);
+}
+int cfx_i_decompress2_impl(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items,
+                           const cfx_second_item* second, float decay, void* stream, unsigned* pre, unsigned pre_val) {
+    return cfx_i_decompress2_checked(ctx, codec, N, C, param, batch, items, second, decay, stream, pre, pre_val);
 }
 
 extern "C" {

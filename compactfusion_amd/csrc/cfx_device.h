@@ -27,6 +27,9 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 struct BatchC { cfx_comp_item it[CFX_MAX_BATCH]; };
 struct BatchD { cfx_decomp_item it[CFX_MAX_BATCH]; };
+// the batches of the second-order launches (include/cfx.h, "Second-order residual"): per item the two second-order states, and the decay
+struct BatchC2 { cfx_comp_item it[CFX_MAX_BATCH]; cfx_second_item s2[CFX_MAX_BATCH]; float decay; };
+struct BatchD2 { cfx_decomp_item it[CFX_MAX_BATCH]; cfx_second_item s2[CFX_MAX_BATCH]; float decay; };
 
 // ---------------------------------------------------------------------------------------------------
 // device helpers
@@ -188,18 +191,24 @@ __device__ __forceinline__ h16x8 habs8(h16x8 v) {
 // everything between d and recv (sign bits, codes, exact sums, scales, packet bytes) is the fp16 path's.  A lane's 8 elements travel as
 // an h16x8 either way - for bf16 the raw 16-bit words, converted where they are used - so registers, parked tiles, loads and stores do
 // not change; the fp16 case of every function below is the expression it replaced.
-struct ElemF16 { static constexpr bool bf16 = false; };
-struct ElemBF16 { static constexpr bool bf16 = true; };
+// Beside the element type the same argument carries the PREDICTOR: first order (the codec sees x - base, the state is base), or - Pred2,
+// fp16 only - second order (include/cfx.h, "Second-order residual"): the codec sees (x - base) - delta_base, and a reconstruction writes two
+// states, new_base = (base + delta_base) + recv and new_delta = fp16(fp32(delta_base + recv) * decay).  A second-order kernel carries the
+// third operand beside the state through its tile loop (h16x8 dv[..]; one element in the first-order kernels, never loaded).
+struct ElemF16 { static constexpr bool bf16 = false; static constexpr bool second = false; };
+struct ElemBF16 { static constexpr bool bf16 = true; static constexpr bool second = false; };
+struct Pred2 { static constexpr bool bf16 = false; static constexpr bool second = true; };
 // bf16 -> fp32 is a shift (the low element of a word) or a mask (the high one); fp32 -> bf16 / fp16 are gfx950's packed converts
 // (v_cvt_pk_bf16_f32, v_cvt_pk_f16_f32: round to nearest even)
 __device__ __forceinline__ f32x2 bf2_f32(unsigned w) {
     return f32x2{__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
 }
 __device__ __forceinline__ unsigned f32_bf2(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
-// d = x - base in the residual domain
+// d = x - base in the residual domain; second order: dd = (x - base) - delta_base, one fp16 rounding per subtraction (main.py:247)
 template <class E>
-__device__ __forceinline__ h16x8 el_diff(h16x8 x, h16x8 b) {
-    if constexpr (!E::bf16) return x - b;
+__device__ __forceinline__ h16x8 el_diff(h16x8 x, h16x8 b, h16x8 dl = (h16x8)(h16)0) {
+    if constexpr (E::second) return (x - b) - dl;
+    else if constexpr (!E::bf16) return x - b;
     else {
         const u32x4 xw = __builtin_bit_cast(u32x4, x), bw = __builtin_bit_cast(u32x4, b);
         h16x8 d;
@@ -226,6 +235,22 @@ __device__ __forceinline__ h16x8 el_state(bool has_base, h16x8 b, h16x8 recv) {
             o[w] = f32_bf2(has_base ? bf2_f32(bw[w]) + r : r);
         }
         return __builtin_bit_cast(h16x8, o);
+    }
+}
+
+// second order: BOTH states of a reconstruction site, from pred = base + delta_base and delta_base (not from base) - the arithmetic of
+// k_residual2_update (cfx_api.hip), expression for expression:  new_base = pred + recv ;  new_delta = fp16(fp32(delta_base + recv) * decay).
+// nd NULL: the reconstruction alone (update_cache = False).  In place (out == base, nd == delta_base): every element is read and
+// written by the one lane that owns it.
+__device__ __forceinline__ void el_state2_store(h16* out, h16* nd, h16x8 b, h16x8 dl, h16x8 recv, float decay) {
+    const h16x8 pred = b + dl;
+    st8nt(out, pred + recv);
+    if (nd) {
+        const h16x8 s = dl + recv;
+        h16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = (h16)((float)s[k] * decay);
+        st8nt(nd, o);
     }
 }
 

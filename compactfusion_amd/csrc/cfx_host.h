@@ -25,6 +25,8 @@ struct CompressCall {
     unsigned* tick;
     unsigned slot;
     int stream_cus, R, P;
+    const cfx_second_item* second;   // != NULL: second-order states of the items (cfx_compress_batch_res2; 1-bit / 2-bit, fp16) and their decay
+    float decay;
 };
 extern "C" {
 CFX_HIDDEN int cfx_i_topk_compress(CompressCall& cc);
@@ -32,6 +34,7 @@ CFX_HIDDEN int cfx_i_absmean_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_minmax_compress(CompressCall& cc);
 // reconstruction launches of a validated batch (decompress_impl's dispatch); `pre` / `pre_val`: an optional flag word the kernel waits for
 CFX_HIDDEN int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, bool bf16, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
+CFX_HIDDEN int cfx_i_absmean_decompress2(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD2& b, int R, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_minmax_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_topk_decompress(cfx_ctx* ctx, int N, int C, int param, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
 // cfx_api.hip
@@ -41,6 +44,8 @@ CFX_HIDDEN unsigned cfx_i_ticket_slot(cfx_ctx* ctx, void* stream);
 CFX_HIDDEN void cfx_i_fill_p2p(cfx_ctx* ctx, CfxXGate* xg, P2PInline& p);
 CFX_HIDDEN int cfx_i_decompress_checked(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items, void* stream,
                                         unsigned* pre, unsigned pre_val);
+CFX_HIDDEN int cfx_i_decompress2_checked(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items,
+                                         const cfx_second_item* second, float decay, void* stream, unsigned* pre, unsigned pre_val);
 }  // extern "C"
 // (short names the family files were written with)
 #define auto_rows cfx_i_auto_rows

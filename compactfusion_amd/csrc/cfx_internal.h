@@ -246,6 +246,11 @@ struct PlanOp {
     unsigned* own_flag;                              // this rank's "packets of this layer complete" word (in memory the peers have mapped)
     const unsigned* peer_flag[CFX_P2P_MAX_PEERS];    // the peers' words
     int n_peers;
+    // cfx_plan_set_second_order: second-order states of the compress items (c2) and of the reconstruction items (r2: kind 1 the items d,
+    // kinds 9 / 10 the items g), and their decay; second == 0: a first-order op
+    int second;
+    float decay;
+    cfx_second_item c2[CFX_MAX_BATCH], r2[CFX_MAX_BATCH];
 };
 struct PipeSched;
 struct cfx_plan {
@@ -294,7 +299,11 @@ CFX_HIDDEN int cfx_i_decompress_impl(cfx_ctx* ctx, int codec, int N, int C, int 
 // compress_impl in cfx_api.hip; xg->taken == 0 on return: only the compress part was launched
 CFX_HIDDEN int cfx_i_compress_impl(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
                                    int n_ride, const cfx_decomp_item* ride, int n_gated, const cfx_decomp_item* gated,
-                                   void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg = nullptr);
+                                   void* workspace, size_t workspace_bytes, void* stream, CfxXGate* xg = nullptr,
+                                   const cfx_second_item* second = nullptr, float decay = 0.f);
+// second != NULL required: the second-order reconstruction of a batch (cfx_decompress_batch_res2), `pre` as cfx_i_decompress_impl
+CFX_HIDDEN int cfx_i_decompress2_impl(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items,
+                                      const cfx_second_item* second, float decay, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_launch_pipe(cfx_plan* p, hipStream_t s, int N, int C, const int* comp_op, const int* deq_op,
                                  const PipeUnit* dq, const PipeUnit* fin, const PipeUnit* st, int fin_parity, int st_parity,
                                  hipEvent_t done_ev);

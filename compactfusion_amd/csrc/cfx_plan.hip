@@ -444,6 +444,39 @@ int cfx_ipc_free(cfx_ctx* ctx, void* ptr) {
     return hipFree(ptr) == hipSuccess ? CFX_OK : fail(ctx, CFX_ERR_LAUNCH, "hipFree failed");
 }
 
+// Second-order states for an op (include/cfx.h, "Second-order residual"): kept with the op, handed to the second-order launches by the replay.
+int cfx_plan_set_second_order(cfx_plan* p, int op, int n_comp, const cfx_second_item* comp_second, int n_rec, const cfx_second_item* rec_second,
+                              float decay) {
+    if (!p) return CFX_ERR_NULL;
+    const int kind = (op >= 0 && op < p->n) ? p->ops[op].kind : -1;
+    if (kind != 0 && kind != 1 && kind != 9 && kind != 10) return fail(p->ctx, CFX_ERR_BATCH, "plan: second-order states belong to a compress, reconstruction or exchange-layer op");
+    PlanOp* o = &p->ops[op];
+    const int want_comp = kind == 1 ? 0 : o->batch, want_rec = kind == 1 ? o->batch : (kind == 0 ? 0 : o->n_gated);
+    if (n_comp != want_comp || n_rec != want_rec) return fail(p->ctx, CFX_ERR_BATCH, "plan: second-order states: one per compress item and one per reconstruction item of the op");
+    if ((n_comp && !comp_second) || (n_rec && !rec_second)) return fail(p->ctx, CFX_ERR_NULL, "plan: null second-order states");
+    bool bf16 = false;
+    const int id = codec_id(o->codec, &bf16);
+    if ((id != CFX_CODEC_BINARY && id != CFX_CODEC_INT2) || bf16 || (o->flags & CFX_FLAG_NO_EF) || o->n_ride || (kind == 0 && o->n_gated))
+        return fail(p->ctx, CFX_ERR_CODEC, "plan: second-order states need the 1-bit or 2-bit codec, fp16, no CFX_FLAG_NO_EF, no ride-along / gated items");
+    const bool upd = (o->flags & CFX_FLAG_UPDATE_CACHE) != 0;
+    for (int i = 0; i < n_comp; ++i) {
+        if (!o->c[i].base || !comp_second[i].delta_base || (upd && !comp_second[i].new_delta_base)) return fail(p->ctx, CFX_ERR_NULL, "plan: second-order states need base and delta_base (UPDATE_CACHE: new_delta_base)");
+        if (!AL16(comp_second[i].delta_base) || !AL16(comp_second[i].new_delta_base)) return fail(p->ctx, CFX_ERR_ALIGN, "plan: pointers must be 16-byte aligned");
+    }
+    const cfx_decomp_item* rec = kind == 1 ? o->d : o->g;
+    for (int i = 0; i < n_rec; ++i) {
+        if (!rec[i].base || !rec_second[i].delta_base) return fail(p->ctx, CFX_ERR_NULL, "plan: second-order states need base and delta_base");
+        if (!AL16(rec_second[i].delta_base) || !AL16(rec_second[i].new_delta_base)) return fail(p->ctx, CFX_ERR_ALIGN, "plan: pointers must be 16-byte aligned");
+    }
+    for (int i = 0; i < n_comp; ++i) o->c2[i] = comp_second[i];
+    for (int i = 0; i < n_rec; ++i) o->r2[i] = rec_second[i];
+    o->second = 1;
+    o->decay = decay;
+    sched_free(p->sched);          // (a pipelined schedule recognised earlier may have covered the op: built again at the next replay)
+    p->sched = nullptr;
+    return CFX_OK;
+}
+
 int cfx_plan_size(const cfx_plan* p) { return p ? p->n : CFX_ERR_NULL; }
 
 // append a copy of a compress / decompress op of another plan (to build differently ordered schedules from one op set)
@@ -574,8 +607,16 @@ static int plan_run_impl(cfx_plan* p, int first_op, int n_ops, void* stream, boo
         PlanOp* o = &p->ops[i];
         int rc = CFX_OK;
         switch (o->kind) {
-            case 0: rc = compress_impl(p->ctx, o->codec, o->N, o->C, o->param, o->flags, o->batch, o->c, o->n_ride, o->d, o->n_gated, o->g, o->ws, o->ws_bytes, stream); break;
+            case 0:
+                if (o->second) rc = compress_impl(p->ctx, o->codec, o->N, o->C, o->param, o->flags, o->batch, o->c, 0, nullptr, 0, nullptr, o->ws, o->ws_bytes, stream, nullptr, o->c2, o->decay);
+                else rc = compress_impl(p->ctx, o->codec, o->N, o->C, o->param, o->flags, o->batch, o->c, o->n_ride, o->d, o->n_gated, o->g, o->ws, o->ws_bytes, stream);
+                break;
             case 1:
+                if (o->second) {
+                    rc = cfx_i_decompress2_impl(p->ctx, o->codec, o->N, o->C, o->param, o->batch, o->d, o->r2, o->decay, stream,
+                                                o->pre_flag >= 0 ? p->flags + (size_t)o->pre_flag * FLAG_WORDS : nullptr, p->epoch);
+                    break;
+                }
                 rc = cfx_i_decompress_impl(p->ctx, o->codec, o->N, o->C, o->param, o->batch, o->d, stream,
                                            o->pre_flag >= 0 ? p->flags + (size_t)o->pre_flag * FLAG_WORDS : nullptr, p->epoch);
                 break;
@@ -621,6 +662,23 @@ static int plan_run_impl(cfx_plan* p, int first_op, int n_ops, void* stream, boo
                 // its flag kernel would wait for the very launch it is meant to release - so beside the NULL stream only a non-blocking
                 // exchange stream will do.  Everything else runs the same work in order on the run stream: compress ; exchange ; reconstruct.
                 // (the peer-to-peer form needs NO second stream: workgroup 0 of the launch publishes / awaits the flag words itself)
+                if (o->second) {
+                    // second-order states: never a one-launch layer form (two states per reconstruction tile need another tile geometry) -
+                    // compress ; exchange ; reconstruct in stream order on the run stream
+                    rc = compress_impl(p->ctx, o->codec, o->N, o->C, o->param, o->flags, o->batch, o->c, 0, nullptr, 0, nullptr, o->ws, o->ws_bytes, stream, nullptr, o->c2, o->decay);
+                    if (rc != CFX_OK) break;
+                    if (o->kind == 10) rc = launch_flag_exchange(p, o, main_s, nullptr, 0u, 1, p->p2p_sink, 1u, "p2p exchange layer: flag exchange launch (in order)");
+                    else if (o->comm) {
+                        const int r = o->comm->api.AllGather(o->send, o->recv, o->bytes_per_rank, /*ncclUint8*/ 1, o->comm->comm, main_s);
+                        if (r != 0) {
+                            char buf[200];
+                            snprintf(buf, sizeof(buf), "ncclAllGather (exchange layer, in order): %s", o->comm->api.GetErrorString ? o->comm->api.GetErrorString(r) : "error");
+                            return fail(p->ctx, CFX_ERR_LAUNCH, buf);
+                        }
+                    }
+                    if (rc == CFX_OK) rc = cfx_i_decompress2_impl(p->ctx, o->codec, o->N, o->C, o->param, o->n_gated, o->g, o->r2, o->decay, stream, nullptr, 0u);
+                    break;
+                }
                 const bool inline_p2p = o->kind == 10 && cfx_i_has_xlayer_form(o->codec);
                 bool own_stream = inline_p2p || (p->side && (hipStream_t)stream != p->side && !inline_exchange && cfx_i_has_xlayer_form(o->codec) &&
                                                  (cfx_hw_queues_ok() || p->ctx->allow_shared_queues));
@@ -855,7 +913,7 @@ static int plan_build_sched(cfx_plan* p, int first_op, int n_ops) {
         const int ag0 = n_ag;
         while (i < end && p->ops[i].kind == 0) {
             const PlanOp* c = &p->ops[i];
-            if (c->codec != CFX_CODEC_BINARY || (c->flags & CFX_FLAG_UPDATE_CACHE) || c->n_ride || c->n_gated) { ok = false; break; }
+            if (c->codec != CFX_CODEC_BINARY || (c->flags & CFX_FLAG_UPDATE_CACHE) || c->n_ride || c->n_gated || c->second) { ok = false; break; }
             if (L + k == 0) { N = c->N; C = c->C; }
             if (c->N != N || c->C != C) { ok = false; break; }
             ncomp += c->batch;
@@ -868,7 +926,7 @@ static int plan_build_sched(cfx_plan* p, int first_op, int n_ops) {
         }
         if (i < end && p->ops[i].kind == 4) { ok = false; break; }          // relay hops: in-order replay only
         for (int m = 0; m < k; ++m, ++i) {
-            if (i >= end || p->ops[i].kind != 1 || p->ops[i].codec != CFX_CODEC_BINARY || p->ops[i].N != N || p->ops[i].C != C) { ok = false; break; }
+            if (i >= end || p->ops[i].kind != 1 || p->ops[i].codec != CFX_CODEC_BINARY || p->ops[i].N != N || p->ops[i].C != C || p->ops[i].second) { ok = false; break; }
             ndq += p->ops[i].batch;
             deq_op[L + m] = i;
         }

@@ -55,6 +55,24 @@
  *   exchange inside the launch), with the documented fall-backs; cfx_plan_run_pipelined and the rank-K 1-bit codec are fp16 only (a
  *   pipelined replay of bf16 ops runs as cfx_plan_run).
  *
+ * Second-order residual (CFX_CODEC_BINARY and CFX_CODEC_INT2 only, fp16; CompactConfig(residual=2), xfuser/compact/main.py:244-266, :378-384)
+ *   cfx_compress_batch_res2 / cfx_decompress_batch_res2 take, beside each item, a cfx_second_item {delta_base, new_delta_base} and the
+ *   decay factor (CompactConfig.delta_decay_factor, main.py:272-273); cfx_plan_set_second_order attaches the same to a plan op.  The
+ *   predictor is base + delta_base; one fp16 rounding per reference operation:
+ *       dd        = fp16( fp16(x - base) - delta_base )                  what the codec sees (as if base were NULL)
+ *       dd -> recv  exactly the fp16 codec: sign bits / 2-bit codes, exact sums in units of 2^-24, fp16 scales, packet bytes
+ *       new_base  = recon = fp16( fp16(base + delta_base) + recv )
+ *       new_delta = fp16( fp32( fp16(delta_base + recv) ) * fp32(decay) )
+ *   The packet is a plain fp16-path packet of the same codec; cfx_packet_bytes and cfx_workspace_bytes are the codec's.  Results - packet
+ *   bytes, new_base, new_delta - are bit for bit what cfx_residual2_delta ; cfx_compress_batch(base NULL) ; cfx_decompress_batch(base
+ *   NULL) ; cfx_residual2_update produce, in one launch sequence of the codec's own (the second-order kernels read delta_base beside
+ *   base in their tile loops and store both states where the first-order kernels store one; no full-size temporaries).
+ *   In place is allowed: new_base == base, new_delta_base == delta_base.  base and delta_base are required (CFX_ERR_NULL); a
+ *   reconstruction item may have new_delta_base NULL (update_cache = False: recon only); a compress item needs new_base and
+ *   new_delta_base with CFX_FLAG_UPDATE_CACHE and writes only the packet without it.  CFX_ERR_CODEC before any launch: CFX_FLAG_NO_EF
+ *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 5 (those compose cfx_residual2_delta / _update
+ *   around the codec).  The second-order launches report the kernel ids of their first-order twins (cfx_profile_enable).
+ *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
  *   INT4 / INT8: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
  *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
@@ -492,6 +510,31 @@ int       cfx_comm_ring_hop(cfx_comm* comm, const void* send, void* recv, size_t
 int cfx_residual2_delta(cfx_ctx* ctx, const void* x, const void* base, const void* delta_base, void* dd, size_t n, void* stream);
 int cfx_residual2_update(cfx_ctx* ctx, const void* base, const void* delta_base, const void* recv, void* new_base,
                          void* new_delta_base, float decay, size_t n, void* stream);
+
+/* The second-order predictor INSIDE the 1-bit and 2-bit codec launches ("Second-order residual" above): second[i] belongs to items[i].
+ * cfx_compress_batch_res2 = cfx_compress_batch with the codec seeing (x - base) - delta_base and, with CFX_FLAG_UPDATE_CACHE, both states
+ * updated from the call's own packet; cfx_decompress_batch_res2 = cfx_decompress_batch writing recon = (base + delta_base) + recv and,
+ * where new_delta_base is given, the decayed second-order state.  Checks in the order of the first-order calls (null ctx / items /
+ * second, batch, codec / shape, per item: null, alignment; workspace), the second-order refusals (CFX_FLAG_NO_EF, CFX_ELEM_BF16,
+ * codec ids 3 - 5: CFX_ERR_CODEC) with the codec check.  Capturable as the ungated first-order calls are. */
+typedef struct cfx_second_item {
+    const void* delta_base;     /* (N,C) fp16, 16-byte aligned: required */
+    void*       new_delta_base; /* (N,C) fp16, 16-byte aligned; may alias delta_base; NULL (reconstruction items): not written */
+} cfx_second_item;
+int cfx_compress_batch_res2(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
+                            const cfx_second_item* second, float decay, void* workspace, size_t workspace_bytes, void* stream);
+int cfx_decompress_batch_res2(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items,
+                              const cfx_second_item* second, float decay, void* stream);
+/* Attach second-order states to plan op `op`, built by cfx_plan_add_compress, cfx_plan_add_decompress, cfx_plan_add_exchange_layer or
+ * cfx_plan_add_exchange_layer_p2p (1-bit / 2-bit, fp16, no CFX_FLAG_NO_EF, no ride-along or gated items: CFX_ERR_CODEC otherwise),
+ * before cfx_plan_finalize.  comp_second[n_comp] belong to the op's compress items (n_comp = its batch; 0 for a reconstruction op),
+ * rec_second[n_rec] to its reconstruction items (the op's batch for a reconstruction op, n_recon for an exchange layer, 0 for a compress
+ * op); any other count, an op index out of range or another kind of op is CFX_ERR_BATCH.  The op then runs the second-order launches;
+ * an exchange layer with states attached never takes a one-launch layer form: compress ; exchange ; reconstruct in stream order (the
+ * peer-to-peer word exchange as a one-wave kernel), same results.  cfx_plan_copy_op copies the states with the op, cfx_plan_set_input
+ * and cfx_plan_run_x re-point its activations as before. */
+int cfx_plan_set_second_order(cfx_plan* plan, int op, int n_comp, const cfx_second_item* comp_second, int n_rec,
+                              const cfx_second_item* rec_second, float decay);
 
 /* Ring-attention block merge - the consumer side of the exchange (reference xfuser/compact/ring.py:263 calls
  * yunchang.ring.utils.update_out_and_lse, un-vendored; published formula):
