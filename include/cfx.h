@@ -35,6 +35,10 @@
  *   TOPK    [ val N*C/m fp16 | idx N*C/(2m) B : (i1<<4)|i2 per 2m-block of the flat (-1,1024) view ]           slowpath.py:76-79
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
  *   and N odd, int4 with C % 16 == 8 and N/2 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
+ *   INT4 `min` of a channel whose minimum is zero: where zeros of BOTH signs occur among the channel's deltas, `min` may hold either zero
+ *   (+0 or -0: a min reduction keeps the zero it meets first, and the order is the launch form's - waves, then row tiles).  Scale, codes,
+ *   reconstruction and error-feedback state do not depend on it: q * scale >= +0, and (+0) + (-0) = +0.  Every other half of every packet
+ *   is a function of the inputs alone.
  *
  * bf16 activations (CFX_CODEC_BINARY and CFX_CODEC_INT2 only)
  *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,

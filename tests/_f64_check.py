@@ -16,6 +16,21 @@ Bounds (each derived in its own line):
                  |q - clamp(d / s + zp)| <= 0.75 (0.5 for rint).  int4 code q = rint(fp16(fp16(d - min) / s)): the two roundings
                  <= 15 * 2^-11 + 2^-8 < 0.02 -> |q - clamp((d - min) / s)| <= 0.52.  Reconstruction error |decode - d| <= the code bound
                  times s (the decode evaluated in float64 from the packet; int8: where the zero point is not clamped).
+                 The clamp term.  The code bound is about clamp(.): an element whose quotient lies above the top code L = levels - 1 (15,
+                 255) takes L, and its reconstruction then falls short of d by (d - min) - L * s <= (max - min) - L * s, which is
+                 positive whenever the packet's scale s was rounded BELOW (max - min) / L.  With r = (max - min) / (L + 1e-6), the
+                 quantity the scale check above compares s with: (max - min) - L * s = L * (r - s) + 1e-6 * r <= L * |s - r| + 1e-6 * r.
+                 A normal s is within 1.5 * 2^-11 * s of r, the loss within L * 1.5 * 2^-11 * s of a code (the 0.52 / 0.75 and ulp16(d)
+                 hold it); a subnormal s is a whole number of units of 2^-24 and can be half a unit from r, so the loss reaches L / 2
+                 units - several ulp16(d).  So on channels whose packet scale is below 2^-14, and only there, the reconstruction bound
+                 grows by L * |s - r| (the 1e-6 * r left over is < 2^-14 * 16 * 1e-6 < 2^-33, far inside the ulp16(d) >= 2^-24 already
+                 there).  int8: the same with the top code 127 = zp + 255 where the zero point is -128, fewer levels above zero otherwise
+                 (a smaller loss: the term is an upper bound).
+                 Exact quotients.  Where every intermediate of the code's arithmetic is an fp16 value as it stands (int4: d - min and
+                 (d - min) / s; int8: d / s and d / s + zp) no rounding happens before rint, and the code is rint of that value, ties to
+                 even - exactly, not within a bound.
+                 Scale 0 under a non-zero range (a range of one unit): the int4 quotient is +inf above the minimum (code 15) and 0 / 0
+                 at it (NaN -> code 0); every code reconstructs as min, within the one unit of d.
   top-k          the kept index is the FIRST argmax of |d| in its half-block, the kept value is d there bit for bit, every other element
                  of the state equals base (and the kept one equals fp16(base + d)).
 States: the error-feedback state must also equal fp16(base + decode(packet)) bit for bit, decode in fp16 as the codec defines it.
@@ -119,6 +134,26 @@ def _minmax_common(d, scale, levels, what):
     return d64, mn, mx
 
 
+def _clamp_term(s64, mn, mx, levels):
+    """(levels - 1) * |s - (max - min) / (levels - 1 + 1e-6)| on channels whose packet scale is subnormal, 0 elsewhere (module docstring)"""
+    return np.where(s64 < 2.0 ** -14, (levels - 1) * np.abs(s64 - (mx - mn) / (levels - 1 + 1e-6)), 0.0)
+
+
+def _is_f16(v):
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.isfinite(v) & (v.astype(F16).astype(F64) == v)
+
+
+def _exact_codes(q, a, t, lo, hi, what):
+    """the code's arithmetic is rint(fp16(t)), t formed from fp16(a) in one operation (int8: a = d / s, t = a + zp; int4: a = d - min,
+    t = a / s).  Where a and t are fp16 values as they stand, the code is clip(rint(t)), ties to even, exactly."""
+    exact = _is_f16(a) & _is_f16(t)
+    want = np.clip(np.rint(np.where(exact, t, 0.0)), lo, hi)
+    bad = exact & (q.astype(F64) != want)
+    assert not bad.any(), (f"{what} exact quotients: {int(bad.sum())}/{int(exact.sum())} codes differ from rint (ties to even) of an exactly "
+                           "representable quotient")
+
+
 def check_int8(x, base, pkt, state):
     d = _delta(x, base)
     N, C = d.shape
@@ -131,10 +166,12 @@ def check_int8(x, base, pkt, state):
         want_z = np.clip(-128.0 - np.round(mn / s64), -128, 127)
         y = np.clip(d64 / s64 + z64, -128, 127)
     assert np.all(np.abs(z64 - want_z)[live] <= 1), "int8 zero point further than 1 from -128 - round(min / scale)"
+    with np.errstate(divide="ignore", invalid="ignore"):
+        _exact_codes(q, np.where(live, d64 / s64, np.nan), np.where(live, d64 / s64 + z64, np.nan), -128, 127, "int8")
     err = np.where(live, np.abs(q.astype(F64) - y), 0.0)
     assert err.max() <= 0.75, f"int8 codes: {int((err > 0.75).sum())} further than 0.75 from d / scale + zp (worst {err.max():.3f})"
     rec = (q.astype(F64) - z64) * s64
-    lim = 0.75 * s64 + ulp16(d64)
+    lim = 0.75 * s64 + ulp16(d64) + _clamp_term(s64, mn, mx, 256)
     # (only where the zero point is not clamped: with the min far from 0 relative to the range - few rows - the reference's int16 zero
     # point saturates at -128 / 127 and the codes clamp, the code bound above still holds)
     unclamped = live & (np.abs(-128.0 - np.round(np.where(live, mn / np.where(live, s64, 1), 0)) + 0.5) < 127.5)
@@ -158,11 +195,13 @@ def check_int4(x, base, pkt, state):
     s64 = s.astype(F64)
     with np.errstate(divide="ignore", invalid="ignore"):
         y = np.clip((d64 - mn) / s64, 0, 15)
-    y = np.where(s64 == 0, 0.0, y)
+    y = np.where(s64 == 0, np.where(d64 > mn, 15.0, 0.0), y)       # scale 0: +inf above the minimum, 0 / 0 -> 0 at it
+    with np.errstate(divide="ignore", invalid="ignore"):
+        _exact_codes(q, d64 - mn, np.where(s64 > 0, (d64 - mn) / s64, np.nan), 0, 15, "int4")
     err = np.abs(q.astype(F64) - y)
     assert err.max() <= 0.52, f"int4 codes: {int((err > 0.52).sum())} further than 0.52 from (d - min) / scale (worst {err.max():.3f})"
     rec = q.astype(F64) * s64 + mn
-    bad = np.abs(rec - d64) > 0.52 * s64 + ulp16(d64)
+    bad = np.abs(rec - d64) > 0.52 * s64 + ulp16(d64) + _clamp_term(s64, mn, mx, 16)
     assert not bad.any(), f"int4 reconstruction: {int(bad.sum())} elements off d by more than 0.52 scale"
     _state_equals(state, base, ((q.astype(F16) * s).astype(F16) + m).astype(F16), "int4")
 

@@ -6,8 +6,6 @@ codec and legal shape, bit for bit against the oracle (the C oracle above 4M ele
 (c) batches of 1 / 3 / CFX_MAX_BATCH, (d) the gated layer call with error feedback and looped-back peers over rounds, (e) a captured
 graph replayed.  The test proves its own coverage: the layer form and the fallback form of every codec that has both ran.
 Non-finite input: golden G16 (tests/_nonfinite.py) through the plain, the multi-launch and the layer forms."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -15,41 +13,11 @@ import torch
 import _domain_cases as D
 import _f64_check as F
 import _nonfinite as NF
-from oracle import c_oracle as CO
-from oracle import ref_np as R
+from _gpu_codec import BIG, KID_LAYER, _gated_layer, _profile, dev, host, inputs, oracle, same_bits, same_packet
 
 pytestmark = pytest.mark.gpu
 
 F16 = np.float16
-BIG = 4 << 20                     # elements: above, the C oracle (OpenMP) instead of numpy
-KID_LAYER = 31                    # csrc/cfx_internal.h KID_ABSMEAN_COMPRESS_GATED: every codec's layer launch
-same_bits = NF.same_bits
-
-
-def dev(a16):
-    return torch.from_numpy(np.ascontiguousarray(a16).view(np.int16)).view(torch.float16).cuda()
-
-
-def host(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
-
-
-def inputs(seed, N, C):
-    rng = np.random.default_rng(seed)
-    base = rng.standard_normal((N, C)).astype(F16)
-    x = (base.astype(np.float32) + 0.1 * rng.standard_normal((N, C)).astype(np.float32)).astype(F16)
-    return x, base
-
-
-def oracle(name, x, base, param, N, C, ef=True):
-    """(packet words, new state) of one residual compress"""
-    if N * C > BIG:
-        CO.set_num_threads(16)
-        pkt, nb = CO.compress(name, x, base, N, C, param, update=True, ef=ef)
-        return np.asarray(pkt).view(np.uint16).reshape(-1), np.asarray(nb).view(np.uint16).reshape(N, C)
-    with np.errstate(invalid="ignore", over="ignore"):
-        pkt, nb = R.residual_compress(name, x, base, param, ef=ef) if base is not None else R.compress(name, x, None, param)
-    return np.asarray(pkt).view(np.uint16), R.bits(nb)
 
 
 def _cases(pool=None):
@@ -68,20 +36,6 @@ def _defaults():
     K.set_rows_per_tile(0)
 
 
-def _profile(ctx, lib, fn):
-    """kernel ids of what fn launched"""
-    torch.cuda.synchronize()
-    assert lib.cfx_profile_enable(ctx, 64, 0xffffffff, 1) == 0
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ids, ms = (ctypes.c_int * 64)(), (ctypes.c_float * 64)()
-        n = lib.cfx_profile_read(ctx, ids, ms, 64)
-    finally:
-        lib.cfx_profile_enable(ctx, 0, 0, 1)
-    return [ids[i] for i in range(n)]
-
-
 # ---- (a) the plain calls ----
 @pytest.mark.parametrize("name,cid,param,N,C", _cases())
 def test_plain(name, cid, param, N, C):
@@ -92,7 +46,7 @@ def test_plain(name, cid, param, N, C):
     pkt, nb = K.compress(cid, xd, bd, N, C, param, update_cache=True)
     torch.cuda.synchronize()
     hp, hn = host(pkt), host(nb).reshape(N, C)
-    same_bits(hp, pkt_ref, "packet")
+    same_packet(name, hp, pkt_ref, x, base, "packet")
     same_bits(hn, nb_ref, "sender state")
     F.check(name, param, x, base, hp, hn)
     rec = K.decompress(cid, pkt, bd, N, C, param)
@@ -101,17 +55,17 @@ def test_plain(name, cid, param, N, C):
     pkt2, nb2 = K.compress(cid, xd, bd, N, C, param, update_cache=False)
     torch.cuda.synchronize()
     assert nb2 is None
-    same_bits(host(pkt2), pkt_ref, "packet (update_cache off)")
+    same_packet(name, host(pkt2), pkt_ref, x, base, "packet (update_cache off)")
     pkt3, nb3 = K.compress(cid, xd, bd, N, C, param, update_cache=True, ef=False)
     torch.cuda.synchronize()
-    same_bits(host(pkt3), pkt_ref, "packet (ef off)")
+    same_packet(name, host(pkt3), pkt_ref, x, base, "packet (ef off)")
     same_bits(host(nb3), x.view(np.uint16), "state (ef off) == x")
     # base=None: the codec on x itself
     p0_ref, r0_ref = oracle(name, x, None, param, N, C)
     p0, r0 = K.compress(cid, xd, None, N, C, param, update_cache=True)
     rec0 = K.decompress(cid, p0, None, N, C, param)
     torch.cuda.synchronize()
-    same_bits(host(p0), p0_ref, "packet (base None)")
+    same_packet(name, host(p0), p0_ref, x, None, "packet (base None)")
     same_bits(host(r0), r0_ref, "state (base None)")
     same_bits(host(rec0), r0_ref, "reconstruction (base None)")
 
@@ -129,7 +83,7 @@ def test_finalize_off_and_row_tiles(name, cid, param, N, C):
         pkt, nb = K.compress(cid, xd, bd, N, C, param, update_cache=True)
         rec = K.decompress(cid, pkt, bd, N, C, param)
         torch.cuda.synchronize()
-        same_bits(host(pkt), pkt_ref, f"packet (finalize off, rows {rows})")
+        same_packet(name, host(pkt), pkt_ref, x, base, f"packet (finalize off, rows {rows})")
         same_bits(host(nb), nb_ref, f"sender state (finalize off, rows {rows})")
         same_bits(host(rec), nb_ref, f"reconstruction (finalize off, rows {rows})")
     K.set_fused_finalize(True)
@@ -137,7 +91,7 @@ def test_finalize_off_and_row_tiles(name, cid, param, N, C):
         K.set_rows_per_tile(rows)
         pkt, nb = K.compress(cid, xd, bd, N, C, param, update_cache=True)
         torch.cuda.synchronize()
-        same_bits(host(pkt), pkt_ref, f"packet (rows {rows})")
+        same_packet(name, host(pkt), pkt_ref, x, base, f"packet (rows {rows})")
         same_bits(host(nb), nb_ref, f"sender state (rows {rows})")
 
 
@@ -157,57 +111,12 @@ def test_batches(name, cid, param, N, C, B):
     K.decompress_batch(cid, pks, bs, recs, N, C, param)
     torch.cuda.synchronize()
     for i, (p_ref, n_ref) in enumerate(refs):
-        same_bits(host(pks[i]), p_ref, f"packet item {i}/{B}")
+        same_packet(name, host(pks[i]), p_ref, ins[i][0], ins[i][1], f"packet item {i}/{B}")
         same_bits(host(nbs[i]), n_ref, f"sender state item {i}/{B}")
         same_bits(host(recs[i]), n_ref, f"reconstruction item {i}/{B}")
 
 
-# ---- (d) the gated layer call: own error feedback + looped-back peers, over rounds ----
-def _gated_layer(name, cid, param, N, C, B, NP, rounds, seed, check=True):
-    """cfx_compress_batch_gated as test_gated_int2_layer_in_one_launch drives it; returns the kernel ids of the first round"""
-    from compactfusion_amd import _lib, codecs as K
-    lib = _lib.load()
-    ctx = K.context(0)
-    ins = [inputs(seed + i, N, C) for i in range(B)]
-    xs = [x for x, _ in ins]
-    xd = [dev(x) for x in xs]
-    own = [dev(b) for _, b in ins]
-    src = [i % B for i in range(NP)]
-    peer = [dev(ins[src[g]][1]) for g in range(NP)]
-    pk = [torch.zeros(K.packet_halves(cid, N, C, param), dtype=torch.float16, device="cuda") for _ in range(B)]
-    ws = K.workspace(cid, N, C, param, B, 0)
-    wsp, wsn = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
-    sh = torch.cuda.current_stream().cuda_stream
-    comp = (_lib.CompItem * B)(*[_lib.CompItem(xd[i].data_ptr(), own[i].data_ptr(), own[i].data_ptr(), pk[i].data_ptr()) for i in range(B)])
-    gated = (_lib.DecompItem * NP)(*[_lib.DecompItem(pk[src[g]].data_ptr(), peer[g].data_ptr(), peer[g].data_ptr()) for g in range(NP)])
-
-    def go():
-        assert lib.cfx_compress_batch_gated(ctx, cid, N, C, param, _lib.FLAG_UPDATE_CACHE, B, comp, 0, None, NP, gated, wsp, wsn, sh) == 0
-    ostate = [b.view(np.uint16).copy() for _, b in ins]
-    ids = None
-    for t in range(rounds):
-        if ids is None:
-            ids = _profile(ctx, lib, go)
-        else:
-            go()
-        if not check:
-            continue
-        opk = []
-        for i in range(B):
-            p, nb = oracle(name, xs[i], ostate[i].view(F16), param, N, C)
-            opk.append(p)
-            ostate[i] = nb.copy()
-        torch.cuda.synchronize()
-        assert lib.cfx_gate_errors(ctx) == 0
-        for i in range(B):
-            same_bits(host(pk[i]), opk[i], f"packet round {t} item {i}")
-            same_bits(host(own[i]), ostate[i], f"own state round {t} item {i}")
-        for g in range(NP):
-            same_bits(host(peer[g]), ostate[src[g]], f"peer state round {t} peer {g}")
-    torch.cuda.synchronize()
-    return ids
-
-
+# ---- (d) the gated layer call: own error feedback + looped-back peers, over rounds (_gpu_codec._gated_layer) ----
 def _form(ids):
     return "layer" if ids == [KID_LAYER] else "fallback"
 
@@ -238,7 +147,7 @@ def test_minmax_tile_count_crossing(name, cid):
         ids = _profile(ctx, lib, lambda: K.compress_batch(cid, xs, bs, bs, pks, N, C, 0, update_cache=True))
         forms.add(KID_LAYER in ids)
         for i in range(B):
-            same_bits(host(pks[i]), refs[i][0], f"packet batch {B} item {i}")
+            same_packet(name, host(pks[i]), refs[i][0], ins[i][0], ins[i][1], f"packet batch {B} item {i}")
             same_bits(host(bs[i]), refs[i][1], f"state batch {B} item {i}")
         del xs, bs, pks
         torch.cuda.empty_cache()
@@ -273,8 +182,9 @@ def test_graph_replay(name, cid, param, N, C):
         torch.cuda.synchronize()
         graph.replay()
         torch.cuda.synchronize()
+        before = ostate
         p_ref, ostate = oracle(name, x, ostate.view(F16), param, N, C)
-        same_bits(host(pkt), p_ref, f"packet replay {r}")
+        same_packet(name, host(pkt), p_ref, x, before.view(F16), f"packet replay {r}")
         same_bits(host(state), ostate, f"sender state replay {r}")
         same_bits(host(peer), ostate, f"peer state replay {r}")
 
