@@ -21,6 +21,7 @@ class Codec(IntEnum):
     INT4 = 3     # residual int4 (compress_quantize.py:522-640 on delta)
     INT8 = 4     # residual int8 (compress_quantize.py:428-484 on delta)
     TOPK = 5     # COMPACT_COMPRESS_TYPE.SPARSE, param = sparse_ratio m
+    INT2_MINMAX = 6   # residual 4-level per-channel min/max (compress_quantize.py:386-426 on delta), four rows per byte
 
 
 _ctx = {}

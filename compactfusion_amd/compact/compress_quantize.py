@@ -129,6 +129,24 @@ def dequantize_int4(packed_tensor: torch.Tensor, scale: torch.Tensor, min_val: t
     return codecs.decompress(K.INT4, _cat_packet(packed_tensor, scale, min_val), None, N2 * 2, C)
 
 
+# ---- 4-level min/max (extension: the reference only simulates it, sim_int2_minmax above) ---------------------------
+def quantize_int2_minmax(input_tensor: torch.Tensor):
+    """-> packed (N/4, C) uint8 [bits 2h..2h+1 of byte [k][c] = row 4k+h], scale (1,C), min (1,C).  The native INT2_MINMAX wire codec
+    at residual 0; a channel whose values are all equal gets scale 0 and codes 0 (sim_int2_minmax returns NaN there)."""
+    x = _nc(input_tensor)
+    N, C = x.shape
+    assert N % 4 == 0, f"Dimension N (0) size must be a multiple of 4 for INT2_MINMAX packing, got {N}"
+    pkt, _ = codecs.compress(K.INT2_MINMAX, x, None, N, C, update_cache=False)
+    qh = N * C // 8
+    return pkt[:qh].view(torch.uint8).view(N // 4, C), pkt[qh:qh + C].view(1, C), pkt[qh + C:].view(1, C)
+
+
+def dequantize_int2_minmax(packed_tensor: torch.Tensor, scale: torch.Tensor, min_val: torch.Tensor):
+    assert packed_tensor.dtype == torch.uint8 and scale.dtype == torch.half and min_val.dtype == torch.half
+    N4, C = packed_tensor.shape
+    return codecs.decompress(K.INT2_MINMAX, _cat_packet(packed_tensor, scale, min_val), None, N4 * 4, C)
+
+
 def sim_int4(input_tensor: torch.Tensor, dim):
     x = _nc(input_tensor)
     if dim == 1:

@@ -1,4 +1,4 @@
-// libcfx.so - the min/max codec family: residual int8 and int4 (compress_quantize.py:428-484, :522-640): stand-alone kernels, the one-launch
+// libcfx.so - the min/max codec family: residual int8, int4 and the 4-level INT2_MINMAX (compress_quantize.py:428-484, :522-640, :386-426): stand-alone kernels, the one-launch
 // compress, the layer launch (k_minmax_layer).  Shared device code: cfx_device.h; the C-ABI and the dispatch: cfx_api.hip.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -97,12 +97,17 @@ __device__ __forceinline__ h16 hdiv_r(h16 a, float bf, float rb) {
 __device__ __forceinline__ bool hisnan(h16 a) { return a != a; }
 
 // int4 : scale = fp16(fp16(max-min)/15.000001f), min                              compress_quantize.py:556-558
+// int2 min/max : scale = fp16(fp16(max-min)/3.000001f), min                       compress_quantize.py:402-404
 // int8 : scale = fp16(fp16(max-min)/255.0f), zp = clamp(-128 - round(min/scale)) -> int16          :455-463
 __device__ __forceinline__ void minmax_write_scales(const cfx_comp_item& it, int N, int C, int codec, int c, h16 mn, h16 mx) {
     const h16 rng = mx - mn;
     if (codec == CFX_CODEC_INT4) {
         h16* S = (h16*)((char*)it.packet + (size_t)(N / 2) * C);
         S[c] = (h16)((float)rng / 15.000001f);
+        S[C + c] = mn;
+    } else if (codec == CFX_CODEC_INT2_MINMAX) {
+        h16* S = (h16*)((char*)it.packet + (size_t)(N / 4) * C);
+        S[c] = (h16)((float)rng / 3.000001f);
         S[C + c] = mn;
     } else {
         h16* S = (h16*)((char*)it.packet + (size_t)N * C);
@@ -197,23 +202,27 @@ __global__ __launch_bounds__(NTHR) void k_minmax_compress(BatchC batch, int N, i
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The min/max codecs' layer in ONE launch (cfx_compress_batch_gated / the exchange-layer ops, codecs INT4 and INT8) - what the 1-bit and
+// The min/max codecs' layer in ONE launch (cfx_compress_batch_gated / the exchange-layer ops, codecs INT4, INT8 and INT2_MINMAX) - what the 1-bit and
 // 2-bit codecs have had: the statistics tile stays in REGISTERS, the scales are finalised inside the launch, every statistics workgroup
-// then quantises its own tile from those registers (x and the state are read ONCE: 6.5 / 7.0 B per element is what moves), and the
+// then quantises its own tile from those registers (x and the state are read ONCE: 6.5 / 7.0 / 6.25 B per element is what moves), and the
 // reconstruction of the peers' tensors waits in the same launch, state tiles preloaded, for the packets.
 //   S  tile (32 rows x 512 channels, 8 waves): load x, state -> d = x - state -> per-channel {min, max} partial of the tile, published
-//      write-through -> ticket of the column block; the block's last arriver reduces the P partials, writes scale / min (int4) or scale /
+//      write-through -> ticket of the column block; the block's last arriver reduces the P partials, writes scale / min (int4, INT2_MINMAX) or scale /
 //      zero point (int8) into the packet (compress_quantize.py:452-463, :552-558) and raises the block's COLUMN GATE.  The scales of a
 //      tile depend on its column block only (there is no tensor-wide statistic), so a tile waits for the P tiles of its own block, not
-//      for the launch.  Then: codes from registers (arithmetic of k_int4_quant / k_int8_quant), published as 16-byte write-through
+//      for the launch.  Then: codes from registers (arithmetic of k_int4_quant / k_int8_quant / k_int2mm_quant), published as 16-byte write-through
 //      stores through an LDS transpose, one arrival on the codes gate, error-feedback state last (nobody waits for it).
-//   D  tile (112 rows x 512 channels): state rows into registers, wait for the gate (the launch's own codes gate, or the external word an
+//   D  tile (up to 112 rows x 512 channels; INT2_MINMAX: up to 128, whole row quads per wave - MML_KC / MML_KC4): state rows into registers, wait for the gate (the launch's own codes gate, or the external word an
 //      exchange stream sets once the peers' packets have arrived), codes + scales through L2-bypassing loads, finish from registers.
 // S workgroups precede D in dispatch order and wait only for each other: all of them must be CO-RESIDENT (the host checks; otherwise the
 // multi-launch forms run).  Column gates hold a per-stream launch sequence number (monotonic, raised with atomic max: never reset).
 // ---------------------------------------------------------------------------------------------------
 #define MML_NW FUSED_NW
 #define MML_KC 14              // rows of a D tile a wave holds in registers (int4: 7 row pairs)
+#define MML_KC4 16             // ... of the 4-level codec: 4 row quads (14 is no multiple of 4; 16 state rows are 64 registers, within the 128 the S tile needs anyway)
+// The family's members by RPC, the rows one code row (C bytes) of the packet holds: 1 = int8, 2 = int4 (16 levels), 4 = INT2_MINMAX (4 levels)
+__host__ __device__ constexpr int mml_rpc(int codec) { return codec == CFX_CODEC_INT4 ? 2 : codec == CFX_CODEC_INT2_MINMAX ? 4 : 1; }
+__host__ __device__ constexpr int mml_kc(int rpc) { return rpc == 4 ? MML_KC4 : MML_KC; }
 #define MML_MAX_P 64           // row tiles per column block (one poll load per lane of a wave)
 #define MML_MAX_P_TALL 128     // ... of the tall form (two poll loads per lane)
 #define MML_NRED 8             // tall form: tiles 0 .. 7 of a column block reduce 64 of its 512 channels each
@@ -241,14 +250,15 @@ struct MinMaxLayerArgs {
     Probe probe;                      // developer build: 16 words per workgroup (100 MHz wall clock per phase; word 7: 1 = S tile, 4 = D tile)
 };
 #define MML_STAMP(i) st.at(i)
-// received values of 8 channels of row h of a code row (int8: h = 0): k_int8_dequant / k_int4_dequant arithmetic
-template <bool INT4>
+// received values of 8 channels of row h of a code row (int8: h = 0): k_int8_dequant / k_int4_dequant / k_int2mm_dequant arithmetic
+template <int RPC>
 __device__ __forceinline__ h16x8 minmax_recv(u64 codes, int h, h16x8 sc, h16x8 mz) {
+    constexpr int BITS = 8 / RPC;
     h16x8 qh;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-        qh[i] = INT4 ? (h16)(float)((codes >> (8 * i + 4 * h)) & 15u) : (h16)(float)(int)(signed char)(codes >> (8 * i));
-    return INT4 ? (qh * sc + mz) : ((qh - mz) * sc);
+        qh[i] = RPC > 1 ? (h16)(float)((codes >> (8 * i + BITS * h)) & ((1u << BITS) - 1u)) : (h16)(float)(int)(signed char)(codes >> (8 * i));
+    return RPC > 1 ? (qh * sc + mz) : ((qh - mz) * sc);
 }
 __device__ __forceinline__ u64 ld_wt_or_sys(const u64* p, bool remote) { return remote ? ld_sys(p) : ld_wt(p); }
 __device__ __forceinline__ h16x8 ld8_pub(const u16* p, bool remote) {
@@ -259,10 +269,10 @@ __device__ __forceinline__ h16x8 ld8_pub(const u16* p, bool remote) {
     return __builtin_bit_cast(h16x8, vb);
 }
 // scale vectors of 8 channels out of a packet other workgroups (or another GPU) published; int8: zp as fp16 values
-template <bool INT4>
+template <int RPC>
 __device__ __forceinline__ void minmax_ld_scales(const unsigned char* pk, int N, int C, int cc, bool remote, h16x8& sc, h16x8& mz) {
-    if (INT4) {
-        const u16* S = (const u16*)(pk + (size_t)(N / 2) * C);
+    if (RPC > 1) {
+        const u16* S = (const u16*)(pk + (size_t)(N / RPC) * C);
         sc = ld8_pub(S + cc, remote);
         mz = ld8_pub(S + C + cc, remote);
     } else {
@@ -273,12 +283,12 @@ __device__ __forceinline__ void minmax_ld_scales(const unsigned char* pk, int N,
         for (int i = 0; i < 8; ++i) mz[i] = (h16)(float)(short)zb[i];
     }
 }
-// scale and min (int4) / scale and zero point (int8) of one channel from its {min, max}: compress_quantize.py:556-558 / :455-463
-template <bool INT4>
+// scale and min (int4, 4-level) / scale and zero point (int8) of one channel from its {min, max}: compress_quantize.py:556-558 / :402-404 / :455-463
+template <int RPC>
 __device__ __forceinline__ void minmax_scale_of(h16 mn, h16 mx, h16& scale, u16& second) {
     const h16 rng = mx - mn;
-    if (INT4) {
-        scale = (h16)((float)rng / 15.000001f);
+    if (RPC > 1) {
+        scale = (h16)((float)rng / (RPC == 2 ? 15.000001f : 3.000001f));
         second = hbits(mn);
     } else {
         scale = (h16)((float)rng / 255.000001f);
@@ -304,12 +314,13 @@ __device__ __forceinline__ void minmax_scale_of(h16 mn, h16 mx, h16& scale, u16&
 // (the compiler spilled 12 / 80 bytes a lane to scratch: tools/resource_usage.py).  x itself is dead once d exists; without error
 // feedback (the state becomes x) the last pass reads the tile of x again.
 #define MML_PARK 4
-template <bool INT4, int RW>
+template <int RPC, int RW>
 __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, const MinMaxLayerArgs& a, int z, int bx, int by, u64 (*sm)[TILE_C],
                                                     u32x4* park) {
     constexpr int NW = MML_NW;
-    constexpr int RPC = INT4 ? 2 : 1;          // rows per code row
-    constexpr int CR = RW / RPC;               // code rows a wave holds
+    constexpr int CR = RW / RPC;               // code rows a wave holds (RPC = rows per code row)
+    constexpr int BITS = 8 / RPC;
+    constexpr bool AFFINE = RPC > 1;           // q * scale + min (int4, 4-level); int8: (q - zp) * scale
     const int N = a.N, C = a.C;
     const TileCoord t = tile_coord_at(bx, by, N, C, a.R);
     const h16* x = (const h16*)it.x;
@@ -387,7 +398,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
     MML_STAMP(1);                                           // tile loaded, partial issued
     const size_t fbase = ((size_t)z * a.CB + bx) * a.P;
     unsigned char* pk = (unsigned char*)it.packet;
-    u16* S = (u16*)(pk + (INT4 ? (size_t)(N / 2) * C : (size_t)N * C));
+    u16* S = (u16*)(pk + (size_t)(N / RPC) * C);
     h16 scale;
     u16 second;
     constexpr int NB = RW == 4 ? 16 : 8;                    // partials in flight per thread (registers: the tile stays live)
@@ -431,7 +442,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
                 hi = hmax_nan(b0, hi);
             }
         }
-        minmax_scale_of<INT4>(lo, hi, scale, second);
+        minmax_scale_of<RPC>(lo, hi, scale, second);
         if (by == 0 && ch < C && !failed) {                    // the block's scales into the packet: once
             st_wt(S + ch, hbits(scale));
             st_wt(S + C + ch, second);
@@ -473,7 +484,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
                 }
                 h16 sc1;
                 u16 sec1;
-                minmax_scale_of<INT4>(lo, hi, sc1, sec1);
+                minmax_scale_of<RPC>(lo, hi, sc1, sec1);
                 if (chr < C && !failed) {
                     st_wt(&sca[chr], tag | (unsigned)hbits(sc1) | ((unsigned)sec1 << 16));
                     st_wt(S + chr, hbits(sc1));                 // (the packet's copy: for the receivers, behind this tile's codes flag)
@@ -514,7 +525,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
     {
         const u16x8 s8 = *(const u16x8*)(sl + t.lane * 8), m8 = *(const u16x8*)(sl + TILE_C + t.lane * 8);
         sc = __builtin_bit_cast(h16x8, s8);
-        if (INT4) mz = __builtin_bit_cast(h16x8, m8);
+        if (AFFINE) mz = __builtin_bit_cast(h16x8, m8);
         else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) mz[i] = (h16)(float)(short)m8[i];
@@ -524,7 +535,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
     // ---- own tile: codes from registers ----
     u64* stage = &sm[0][0] + (size_t)t.w * CR * 64;         // this wave's CR code rows x 64 lanes x 8 bytes (same wave writes and reads: in order)
     {
-        // codes exactly as k_int4_quant / k_int8_quant compute them, channel by channel: the division by the channel's scale as
+        // codes exactly as k_int4_quant / k_int2mm_quant / k_int8_quant compute them, channel by channel: the division by the channel's scale as
         // hdiv_r with one reciprocal per channel - this loop is the kernel's instruction count (tall tensors: it ran at the VALU's pace)
         u64 cj[CR];
 #pragma unroll
@@ -534,14 +545,14 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
             const float bf = (float)sc[i], rb = __builtin_amdgcn_rcpf(bf);
 #pragma unroll
             for (int j = 0; j < CR; ++j) {
-                if (INT4) {
+                if (AFFINE) {
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const h16 d = dk[2 * j + h][i];
+                    for (int h = 0; h < RPC; ++h) {
+                        const h16 d = dk[RPC * j + h][i];
                         h16 v = hrint(hdiv_r(d - mz[i], bf, rb));
                         v = __builtin_fmaxf16(v, (h16)0);              // (NaN -> 0, as k_int4_quant's explicit test)
-                        v = __builtin_fminf16(v, (h16)15.0f);
-                        cj[j] |= (u64)((unsigned)(unsigned short)v & 15u) << (8 * i + 4 * h);
+                        v = __builtin_fminf16(v, (h16)(float)((1 << BITS) - 1));
+                        cj[j] |= (u64)((unsigned)(unsigned short)v & ((1u << BITS) - 1u)) << (8 * i + BITS * h);
                     }
                 } else {
                     const h16 d = dk[j][i];
@@ -558,7 +569,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
     }
     {
         // a code row of the tile is 512 bytes = 32 lanes x 16 bytes; lanes [0, 32) take the even code rows of the wave, [32, 64) the odd ones
-        const int crows = INT4 ? N / 2 : N;
+        const int crows = N / RPC;
 #pragma unroll
         for (int jj = 0; jj < CR; jj += 2) {
             const int j = jj + (t.lane >> 5), seg = t.lane & 31;
@@ -584,7 +595,7 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
                 if (rv[q]) {
                     h16x8 o;
                     if (ef) {
-                        const h16x8 recv = minmax_recv<INT4>(stage[j * 64 + t.lane], h, sc, mz);
+                        const h16x8 recv = minmax_recv<RPC>(stage[j * 64 + t.lane], h, sc, mz);
                         const h16x8 b = q < RREG ? bk[q < RREG ? q : 0] : __builtin_bit_cast(h16x8, park[(q - RREG) * (NW * 64) + threadIdx.x]);
                         o = base ? (b + recv) : recv;
                     } else o = ld8nt(x + (size_t)row * C + cc);
@@ -598,11 +609,11 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
     }
 }
 
-template <bool INT4>
+template <int RPC>
 __device__ __forceinline__ void minmax_layer_d_tile(const cfx_decomp_item& it, const MinMaxLayerArgs& a, int item, int bx, int by) {
     constexpr int NW = MML_NW;
-    constexpr int RPC = INT4 ? 2 : 1;
-    constexpr int KC = MML_KC / RPC;           // code rows a wave holds
+    constexpr int KCR = mml_kc(RPC);           // rows a wave holds
+    constexpr int KC = KCR / RPC;              // code rows a wave holds
     const int N = a.N, C = a.C;
     const TileCoord t = tile_coord_at(bx, by, N, C, a.g_R);
     const unsigned char* pk = (const unsigned char*)it.packet;
@@ -614,7 +625,7 @@ __device__ __forceinline__ void minmax_layer_d_tile(const cfx_decomp_item& it, c
     MML_STAMP(0);
     const int kc = a.g_R / (NW * RPC);         // code rows per wave of THIS launch's tiles (<= KC; uniform)
     bool failed = false;
-    h16x8 bv[MML_KC];
+    h16x8 bv[KCR];
 #pragma unroll
     for (int j = 0; j < KC; ++j)
         if (j < kc) {
@@ -650,8 +661,8 @@ __device__ __forceinline__ void minmax_layer_d_tile(const cfx_decomp_item& it, c
     }
     const bool remote = a.remote != 0;
     h16x8 sc, mz;
-    minmax_ld_scales<INT4>(pk, N, C, cc, remote, sc, mz);
-    const int crows = INT4 ? N / 2 : N;
+    minmax_ld_scales<RPC>(pk, N, C, cc, remote, sc, mz);
+    const int crows = N / RPC;
     u64 qb[KC];
 #pragma unroll
     for (int j = 0; j < KC; ++j)
@@ -666,7 +677,7 @@ __device__ __forceinline__ void minmax_layer_d_tile(const cfx_decomp_item& it, c
             for (int h = 0; h < RPC; ++h) {
                 const int row = t.r0 + (t.w + NW * j) * RPC + h;
                 if (row < t.r1 && t.act) {
-                    const h16x8 recv = minmax_recv<INT4>(qb[j], h, sc, mz);
+                    const h16x8 recv = minmax_recv<RPC>(qb[j], h, sc, mz);
                     st8nt(out + (size_t)row * C + t.c, base ? (bv[j * RPC + h] + recv) : recv);
                 }
             }
@@ -678,10 +689,9 @@ __device__ __forceinline__ void minmax_layer_d_tile(const cfx_decomp_item& it, c
     }
 }
 
-template <bool INT4, int RW>
-__global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer(BatchC batch, BatchD gated, MinMaxLayerArgs a) {
-    __shared__ u64 sm[MML_NW][TILE_C];
-    __shared__ u32x4 park[RW > 4 ? MML_PARK * FUSED_NT : 1];           // RW = 8: 32 KB more, still two workgroups a CU
+// one body for the family (RPC = rows per code row); the kernels below are its instantiations
+template <int RPC, int RW>
+__device__ __forceinline__ void minmax_layer_body(BatchC batch, BatchD gated, MinMaxLayerArgs a, u64 (*sm)[TILE_C], u32x4* park) {
     int b = blockIdx.x;
     // (Tried in round 5 for tall tensors: S and D interleaved column block by column block - S(0) S(1) D(0) S(2) D(1) ... - so that
     // reconstruction tiles stream their state in while statistics tiles sit out their scales' hops.  Config 4: 4.78 ms per step either
@@ -693,7 +703,7 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer(BatchC batch, Batc
         int bx, by;
         if (a.tall) { bx = rem / a.P; by = rem - bx * a.P; }
         else { by = rem / a.CB; bx = rem - by * a.CB; }
-        minmax_layer_s_tile<INT4, RW>(batch.it[z], a, z, bx, by, sm, park);
+        minmax_layer_s_tile<RPC, RW>(batch.it[z], a, z, bx, by, sm, park);
         if (b == 0 && a.p2p.own) p2p_exchange_inline(a.codedone, a.seq, a.n_st, a.p2p, a.xgate, a.xexpect, a.err);     // packets complete = every S tile's codes flag
         return;
     }
@@ -701,7 +711,21 @@ __global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer(BatchC batch, Batc
     const int per = a.CB * a.g_rb;
     const int item = b / per, rem = b - item * per;
     const int ty = rem / a.CB;
-    minmax_layer_d_tile<INT4>(gated.it[item], a, item, rem - ty * a.CB, ty);
+    minmax_layer_d_tile<RPC>(gated.it[item], a, item, rem - ty * a.CB, ty);
+}
+
+template <bool INT4, int RW>
+__global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer(BatchC batch, BatchD gated, MinMaxLayerArgs a) {
+    __shared__ u64 sm[MML_NW][TILE_C];
+    __shared__ u32x4 park[RW > 4 ? MML_PARK * FUSED_NT : 1];           // RW = 8: 32 KB more, still two workgroups a CU
+    minmax_layer_body<INT4 ? 2 : 1, RW>(batch, gated, a, sm, park);
+}
+// the 4-level codec (INT2_MINMAX): four rows per code row, D tiles of up to 128 rows (MML_KC4)
+template <int RW>
+__global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer4(BatchC batch, BatchD gated, MinMaxLayerArgs a) {
+    __shared__ u64 sm[MML_NW][TILE_C];
+    __shared__ u32x4 park[RW > 4 ? MML_PARK * FUSED_NT : 1];
+    minmax_layer_body<4, RW>(batch, gated, a, sm, park);
 }
 
 // int8 quantise (+EF)      compress_quantize.py:465-467 ; EF = dequantize_int8 :482 + main.py:232
@@ -927,6 +951,98 @@ __global__ __launch_bounds__(NTHR) void k_int4_dequant(BatchD batch, int N, int 
     }
 }
 
+// INT2_MINMAX quantise (+EF): k_int4_quant with four levels - one wave step handles the row QUAD (4k .. 4k+3), four rows per byte along N:
+// byte[k][c] = q[4k][c] | q[4k+1][c] << 2 | q[4k+2][c] << 4 | q[4k+3][c] << 6 (compress_quantize.py:406-424 gives the arithmetic; the
+// reference has no packing for it).  R (rows per tile) is a multiple of 4; quad index space = rows/4.
+__global__ __launch_bounds__(NTHR) void k_int2mm_quant(BatchC batch, int N, int C, int R, int flags) {
+    const cfx_comp_item it = batch.it[blockIdx.z];
+    const TileCoord t = tile_coord(N, C, R);
+    unsigned char* q = (unsigned char*)it.packet;
+    const h16* S = (const h16*)(q + (size_t)(N / 4) * C);
+    const h16* M = S + C;
+    const h16* x = (const h16*)it.x;
+    const h16* base = (const h16*)it.base;
+    h16* nb = (h16*)it.new_base;
+    const bool upd = (flags & CFX_FLAG_UPDATE_CACHE) && nb;
+    const bool ef = !(flags & CFX_FLAG_NO_EF);
+    const bool al16 = ((((uintptr_t)S) | ((uintptr_t)M)) & 15) == 0;
+    h16x8 sc = (h16x8)(h16)1.0f, mn = (h16x8)(h16)0;
+    if (t.act) { sc = ld8_tail(S + t.c, al16); mn = ld8_tail(M + t.c, al16); }
+    float scf[8], scr[8];                                    // the channel's scale and its reciprocal: hdiv_r
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { scf[i] = (float)sc[i]; scr[i] = __builtin_amdgcn_rcpf(scf[i]); }
+    const int k0 = t.r0 >> 2, k1 = t.r1 >> 2;
+    for (int k = k0 + t.w; k < k1; k += WAVES) {             // one row QUAD per wave step
+        if (!t.act) continue;
+        h16x8 xv[4], bv[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            xv[h] = ld8nt(x + (size_t)(4 * k + h) * C + t.c);
+            bv[h] = base ? ld8nt(base + (size_t)(4 * k + h) * C + t.c) : (h16x8)(h16)0;
+        }
+        u64 outb = 0;
+        h16x8 qh[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const h16x8 d = xv[h] - bv[h];
+            const h16x8 dm = d - mn;                         // (r - min)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                h16 v = hrint(hdiv_r(dm[i], scf[i], scr[i]));
+                if (hisnan(v)) v = (h16)0;
+                v = v < (h16)0 ? (h16)0 : v;
+                v = v > (h16)3.0f ? (h16)3.0f : v;
+                const unsigned qi = (unsigned)(float)v & 3u;
+                qh[h][i] = (h16)(float)qi;
+                outb |= (u64)qi << (8 * i + 2 * h);
+            }
+        }
+        *reinterpret_cast<u64*>(q + (size_t)k * C + t.c) = outb;
+        if (upd) {
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                h16x8 o;
+                if (ef) {
+                    const h16x8 recv = qh[h] * sc + mn;      // q*scale + min (two roundings; contraction is off)
+                    o = base ? (bv[h] + recv) : recv;
+                } else o = xv[h];
+                st8nt(nb + (size_t)(4 * k + h) * C + t.c, o);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(NTHR) void k_int2mm_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
+    // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
+    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
+    const cfx_decomp_item it = batch.it[blockIdx.z];
+    const TileCoord t = tile_coord(N, C, R);
+    const unsigned char* q = (const unsigned char*)it.packet;
+    const h16* S = (const h16*)(q + (size_t)(N / 4) * C);
+    const h16* M = S + C;
+    const h16* base = (const h16*)it.base;
+    h16* out = (h16*)it.recon;
+    const bool al16 = ((((uintptr_t)S) | ((uintptr_t)M)) & 15) == 0;
+    h16x8 sc = (h16x8)(h16)1.0f, mn = (h16x8)(h16)0;
+    if (t.act) { sc = ld8_tail(S + t.c, al16); mn = ld8_tail(M + t.c, al16); }
+    const int k0 = t.r0 >> 2, k1 = t.r1 >> 2;
+    for (int k = k0 + t.w; k < k1; k += WAVES) {             // one row QUAD per wave step
+        if (!t.act) continue;
+        h16x8 bv[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) bv[h] = base ? ld8nt(base + (size_t)(4 * k + h) * C + t.c) : (h16x8)(h16)0;
+        const u64 qb = *reinterpret_cast<const u64*>(q + (size_t)k * C + t.c);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            h16x8 qh;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) qh[i] = (h16)(float)((qb >> (8 * i + 2 * h)) & 3u);
+            const h16x8 recv = qh * sc + mn;
+            st8nt(out + (size_t)(4 * k + h) * C + t.c, base ? (bv[h] + recv) : recv);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
@@ -951,18 +1067,20 @@ int cfx_i_minmax_compress(CompressCall& cc) {
     const int stream_cus = cc.stream_cus, R = cc.R, P = cc.P;
     (void)tick; (void)slot;
     const dim3 grid(CB, P, batch);
-    const int Rq = auto_rows(ctx, N, C, batch, true);       // apply passes: same tile map as the (unfused) statistics pass
+    int Rq = auto_rows(ctx, N, C, batch, true);             // apply passes: same tile map as the (unfused) statistics pass
+    if (codec == CFX_CODEC_INT2_MINMAX) Rq = (Rq + 3) & ~3; // (a row quad never straddles a tile: tile starts are multiples of 4, as they are even for int4)
     const dim3 gridq(CB, (N + Rq - 1) / Rq, batch);
     (void)grid;
     // ---- the min/max codecs' layer in ONE launch (k_minmax_layer): statistics tile in registers, in-launch scales, codes from registers,
     // gated reconstruction.  Needs every statistics workgroup CO-RESIDENT on the stream's CUs (each waits for its column block's scales
     // holding its tile); otherwise - tall tensors - the multi-launch forms below run (identical results). ----
-    const bool int4 = codec == CFX_CODEC_INT4;
+    const int rpc = mml_rpc(codec);
+    const int kcr = mml_kc(rpc), g_unit = std::max(16, FUSED_NW * rpc);      // a D tile's height: whole code rows for each of its waves
     const int RL = (N + 31) / 32 <= MML_MAX_P / 2 ? 32 : 64;       // S tile height: 32 rows; 64 where that keeps the partials per channel <= MML_MAX_P
     const int PL = (N + RL - 1) / RL;
     bool tall = PL > MML_MAX_P;
-    int g_rb = (N + FUSED_NW * MML_KC - 1) / (FUSED_NW * MML_KC);
-    int g_R = ((N + g_rb - 1) / g_rb + 15) / 16 * 16;
+    int g_rb = (N + FUSED_NW * kcr - 1) / (FUSED_NW * kcr);
+    int g_R = ((N + g_rb - 1) / g_rb + g_unit - 1) / g_unit * g_unit;
     const long n_st = (long)CB * PL * batch;
     long n_g = (long)CB * g_rb * n_gated;
     bool layer = fused && ctx->gated_on && !ctx->dev_probe && C % 16 == 0 && stream_cus >= 128 && ctx->stats_rows == 0 && PL <= MML_MAX_P_TALL &&
@@ -987,11 +1105,12 @@ int cfx_i_minmax_compress(CompressCall& cc) {
         }
     }
     if (layer) {
-        static int per_cu4 = 0, per_cu8 = 0;
-        int& per_cu = int4 ? per_cu4 : per_cu8;
+        static int per_cu_of[3] = {0, 0, 0};
+        int& per_cu = per_cu_of[rpc >> 1];
         if (!per_cu) {
-            const hipError_t oe = int4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer<true, 8>, FUSED_NT, 0)
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer<false, 8>, FUSED_NT, 0);
+            const hipError_t oe = rpc == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer<true, 8>, FUSED_NT, 0)
+                                  : rpc == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer4<8>, FUSED_NT, 0)
+                                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer<false, 8>, FUSED_NT, 0);
             if (oe != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
         }
         const long slots = (long)per_cu * stream_cus;
@@ -1005,7 +1124,7 @@ int cfx_i_minmax_compress(CompressCall& cc) {
             const long per_rb = (long)CB * n_gated, fit = (slots - n_st) / per_rb;      // row tiles per tensor that fit
             if (fit > g_rb) {
                 const int rows = (int)((N + fit - 1) / fit);
-                g_R = std::max(16, (rows + 15) / 16 * 16);
+                g_R = (rows + g_unit - 1) / g_unit * g_unit;
                 g_rb = (N + g_R - 1) / g_R;
                 n_g = (long)CB * g_rb * n_gated;
             }
@@ -1079,10 +1198,12 @@ int cfx_i_minmax_compress(CompressCall& cc) {
         }
         const dim3 g((unsigned)(n_st + n_g));
         if (RL == 32) {
-            if (int4) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<true, 4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
+            if (rpc == 2) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<true, 4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
+            else if (rpc == 4) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer4<4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
             else LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<false, 4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
         } else {
-            if (int4) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<true, 8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
+            if (rpc == 2) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<true, 8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
+            else if (rpc == 4) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer4<8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
             else LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<false, 8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
         }
         return check_launch(ctx, "min/max layer launch");
@@ -1094,6 +1215,7 @@ int cfx_i_minmax_compress(CompressCall& cc) {
         LAUNCH(ctx, KID_MINMAX_FINALIZE, s, k_minmax_finalize, dim3((C + 255) / 256, batch), dim3(1024), 0, s, b, N, C, P, codec, (const u64*)ws, wstride);
     }
     if (codec == CFX_CODEC_INT4) LAUNCH(ctx, KID_INT4_QUANT, s, k_int4_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
+    else if (codec == CFX_CODEC_INT2_MINMAX) LAUNCH(ctx, KID_INT4_QUANT, s, k_int2mm_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
     else LAUNCH(ctx, KID_INT8_QUANT, s, k_int8_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
     if (n_gated) {
         const int rcg = decompress_impl(ctx, codec, N, C, param, n_gated, gated, stream, nullptr, 0u);
@@ -1104,8 +1226,10 @@ int cfx_i_minmax_compress(CompressCall& cc) {
 
 int cfx_i_minmax_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val) {
     hipStream_t s = (hipStream_t)stream;
+    if (codec == CFX_CODEC_INT2_MINMAX) R = (R + 3) & ~3;   // (row quads: see cfx_i_minmax_compress)
     const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, batch);
     if (codec == CFX_CODEC_INT4) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int4_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+    else if (codec == CFX_CODEC_INT2_MINMAX) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int2mm_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
     else LAUNCH(ctx, KID_INT8_DEQUANT, s, k_int8_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
     return check_launch(ctx, "decompress launch");
 }

@@ -32,13 +32,30 @@
  *   INT2    [ codes N*C/4 B : 2-bit (sign<<1|mag) , element j at bits 2(j%4)   | tok N fp16 | chan C fp16 ]   main.py:149-152
  *   INT4    [ codes N*C/2 B : byte [n/2][c] = q[n][c] | q[n+1][c]<<4           | scale C fp16 | min C fp16 ]   compress_quantize.py:566-573
  *   INT8    [ q     N*C   B : int8                                             | scale C fp16 | zp  C int16 ]  compress_quantize.py:463-471
+ *   INT2_MINMAX [ codes N*C/4 B : byte [n/4][c] = q[n][c] | q[n+1][c]<<2 | q[n+2][c]<<4 | q[n+3][c]<<6 | scale C fp16 | min C fp16 ]
+ *           (no wire in the reference, which only simulates it: compress_quantize.py:386-426; INT4's row-per-byte convention, four rows)
  *   TOPK    [ val N*C/m fp16 | idx N*C/(2m) B : (i1<<4)|i2 per 2m-block of the flat (-1,1024) view ]           slowpath.py:76-79
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
- *   and N odd, int4 with C % 16 == 8 and N/2 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
+ *   and N odd, int4 with C % 16 == 8 and N/2 odd, INT2_MINMAX with C % 16 == 8 and N/4 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
  *   INT4 `min` of a channel whose minimum is zero: where zeros of BOTH signs occur among the channel's deltas, `min` may hold either zero
  *   (+0 or -0: a min reduction keeps the zero it meets first, and the order is the launch form's - waves, then row tiles).  Scale, codes,
  *   reconstruction and error-feedback state do not depend on it: q * scale >= +0, and (+0) + (-0) = +0.  Every other half of every packet
  *   is a function of the inputs alone.
+ *
+ * INT2_MINMAX (CFX_CODEC_INT2_MINMAX, param 0): INT4's arithmetic with 4 levels, one fp16 rounding per reference operation
+ *       d      = x - base                                   (base NULL: x)
+ *       mn, mx = per-channel min / max of d over the rows   (NaN-propagating, as int4 / int8)
+ *       scale  = fp16( fp32(fp16(mx - mn)) / 3.000001f )
+ *       q      = clamp( rint( fp16( fp16(d - mn) / scale ) ), 0, 3 )     round half to even; a NaN quotient gives code 0
+ *       recv   = fp16( fp16(q * scale) + mn )
+ *       new_base = base + recv     (CFX_FLAG_NO_EF: x)
+ *   Shapes: C % 8 == 0 and N % 4 == 0 (CFX_ERR_SHAPE otherwise); cfx_packet_bytes = N*C/4 + 4*C; the workspace is INT4's.  The
+ *   signed-zero rule for `min` and the non-finite rules are INT4's (above / "Non-finite input").  On a channel whose deltas are all equal
+ *   the scale is 0 and the quotient NaN: the wire codec stores code 0 and reconstructs `min`, as INT4 does, where the reference's
+ *   sim_int2_minmax returns NaN; everywhere else recv equals sim_int2_minmax(d) bit for bit.  Every launch form INT4 has exists
+ *   (stand-alone, in-launch finalize, the one-launch layer with its gated / exchange forms); the quantise / dequantise kernels report
+ *   INT4's kernel ids (cfx_profile_enable).  Ride-along reconstruction items (cfx_compress_batch_ex, n_ride > 0) stay the 1-bit codec's:
+ *   with codec 6, as with INT4, they are CFX_ERR_CODEC.
  *
  * bf16 activations (CFX_CODEC_BINARY and CFX_CODEC_INT2 only)
  *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,
@@ -54,7 +71,7 @@
  *   Packet layout, cfx_packet_bytes and cfx_workspace_bytes are those of the fp16 codec: a bf16 sender's packet is a valid fp16-path
  *   packet (a receiver may reconstruct it onto an fp16 state with the plain codec id, and the other way round).  Domain as for the
  *   fp16 path: finite inputs with |x - base| < 65504; outside it the result is unspecified (see "Non-finite input").
- *   The bit on codecs 3 - 5, and any other bit above the codec id, is CFX_ERR_CODEC; the sizes of such a codec argument are 0.
+ *   The bit on codecs 3 - 6, and any other bit above the codec id, is CFX_ERR_CODEC; the sizes of such a codec argument are 0.
  *   Every form the fp16 path has exists for bf16 (stand-alone, in-launch finalize, ride-along, one-launch layer forms, the peer-to-peer
  *   exchange inside the launch), with the documented fall-backs; cfx_plan_run_pipelined and the rank-K 1-bit codec are fp16 only (a
  *   pipelined replay of bf16 ops runs as cfx_plan_run).
@@ -74,11 +91,11 @@
  *   In place is allowed: new_base == base, new_delta_base == delta_base.  base and delta_base are required (CFX_ERR_NULL); a
  *   reconstruction item may have new_delta_base NULL (update_cache = False: recon only); a compress item needs new_base and
  *   new_delta_base with CFX_FLAG_UPDATE_CACHE and writes only the packet without it.  CFX_ERR_CODEC before any launch: CFX_FLAG_NO_EF
- *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 5 (those compose cfx_residual2_delta / _update
+ *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6 (those compose cfx_residual2_delta / _update
  *   around the codec).  The second-order launches report the kernel ids of their first-order twins (cfx_profile_enable).
  *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
- *   INT4 / INT8: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
+ *   INT4 / INT8 / INT2_MINMAX: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
  *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
  *   TOPK:        |delta| is ranked as the reference's tl.argmax ranks it: NaN above everything, +inf included; the first NaN wins.
  *   BINARY / INT2: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
@@ -118,7 +135,8 @@ enum cfx_codec {
     CFX_CODEC_INT2 = 2,      /* COMPACT_COMPRESS_TYPE.INT2 fastpath */
     CFX_CODEC_INT4 = 3,      /* per-channel min/max 16 levels, rows paired per byte */
     CFX_CODEC_INT8 = 4,      /* per-channel affine int8, zero point int16 */
-    CFX_CODEC_TOPK = 5       /* COMPACT_COMPRESS_TYPE.SPARSE, param = m in {1,2,4,8,16} */
+    CFX_CODEC_TOPK = 5,      /* COMPACT_COMPRESS_TYPE.SPARSE, param = m in {1,2,4,8,16} */
+    CFX_CODEC_INT2_MINMAX = 6 /* COMPACT_COMPRESS_TYPE.INT2_MINMAX: per-channel min/max 4 levels, four rows per byte; param 0 */
 };
 /* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit and 2-bit codecs; "bf16 activations" above) */
 #define CFX_ELEM_BF16 0x100

@@ -33,10 +33,17 @@ CONFIGS = [
     ("5 SD3 1024^2 SP8 patch-gather top-k 1:8", 5, 8, (512, 1536), 24, 2, 16, False),
     ("5 SD3 1024^2 SP8 patch-gather LOW_RANK r=8", 101, 8, (512, 1536), 24, 2, 16, False),
     ("5 SD3 1024^2 SP8 patch-gather LOW_RANK r=16", 101, 16, (512, 1536), 24, 2, 16, False),
+    # the 4-level min/max codec (INT2_MINMAX, codec 6) at the shapes of the INT4 rows and at the FLUX shard, and - rows 7 - the 2-bit
+    # abs-mean codec and INT4 at the FLUX shard to read it against (no C restatement of codec 6: the check column is n/a for rows 6)
+    ("6a PixArt-a 512^2 SP2 patch-gather INT2_MINMAX (config 2's shard)", 6, 0, (1024, 1152), 28, 2, 4, False),
+    ("6b CogVideoX-5B SP4 ring INT2_MINMAX (config 4's shard)", 6, 0, (4448, 3072), 42, 2, 6, True),
+    ("6c FLUX.1 1024^2 ring 8, INT2_MINMAX (config 3's shard)", 6, 0, (544, 3072), 57, 2, 14, True),
+    ("7a FLUX.1 1024^2 ring 8, INT2 (config 3's shard)", 2, 0, (544, 3072), 57, 2, 14, True),
+    ("7b FLUX.1 1024^2 ring 8, INT4 (config 3's shard)", 3, 0, (544, 3072), 57, 2, 14, True),
 ]
-NAMES = {1: "binary", 3: "int4", 4: "int8", 5: "topk"}
+NAMES = {1: "binary", 2: "int2", 3: "int4", 4: "int8", 5: "topk"}
 # algorithmic bytes per element (compress + error feedback, reconstruct); low-rank: x + state in, state out (6), state in / out (4)
-ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8), 101: (6.0, 4.0)}
+ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8), 6: (6.25, 4.25), 101: (6.0, 4.0)}
 
 
 def alg_bytes(cid, N, C, L, ncomp, nrec, update):
@@ -168,7 +175,7 @@ def gpu_step(cid, param, N, C, L, ncomp, nrec, update, min_steps=20, budget_s=0.
 
 
 def cpu_step(cid, param, N, C, L, ncomp, nrec, update, budget=8.0):
-    if cid >= 100:
+    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX
         return None, 0
     from oracle import c_oracle as CO
     name = NAMES[cid]
