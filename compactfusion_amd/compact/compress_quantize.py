@@ -147,6 +147,30 @@ def dequantize_int2_minmax(packed_tensor: torch.Tensor, scale: torch.Tensor, min
     return codecs.decompress(K.INT2_MINMAX, _cat_packet(packed_tensor, scale, min_val), None, N4 * 4, C)
 
 
+# ---- MXFP4 (extension: not in the reference; include/cfx.h "MXFP4") -----------------------------------------------
+def quantize_mxfp4(input_tensor: torch.Tensor):
+    """-> codes (N, C/2) uint8 [byte [n][j] = code[n][2j] | code[n][2j+1] << 4, code = sign << 3 | E2M1 index], scales (N, C/32) uint8
+    [one E8M0 byte per block of 32 consecutive elements of a row; 0xFF: a block with a NaN or an inf].  The native MXFP4 wire codec at
+    residual 0."""
+    x = _nc(input_tensor)
+    N, C = x.shape
+    assert C % 64 == 0, f"Dimension C (1) size must be a multiple of 64 for MXFP4 blocks, got {C}"
+    pkt, _ = codecs.compress(K.MXFP4, x, None, N, C, update_cache=False)
+    by = pkt.view(torch.uint8)
+    return by[:N * C // 2].view(N, C // 2), by[N * C // 2:].view(N, C // 32)
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor):
+    assert codes.dtype == torch.uint8 and scales.dtype == torch.uint8
+    N, C2 = codes.shape
+    assert scales.shape == (N, C2 // 16)
+    return codecs.decompress(K.MXFP4, _cat_packet(codes, scales), None, N, C2 * 2)
+
+
+def sim_mxfp4(input_tensor: torch.Tensor):
+    return dequantize_mxfp4(*quantize_mxfp4(input_tensor))
+
+
 def sim_int4(input_tensor: torch.Tensor, dim):
     x = _nc(input_tensor)
     if dim == 1:

@@ -164,6 +164,8 @@ def _native(compress_type: T) -> Tuple[int, int]:
         return int(codecs.Codec.INT8), 0
     if compress_type == T.INT2_MINMAX:
         return int(codecs.Codec.INT2_MINMAX), 0
+    if compress_type == T.MXFP4:
+        return int(codecs.Codec.MXFP4), 0
     if compress_type == T.SPARSE:
         assert _config.sparse_ratio is not None, "sparse_ratio must be provided for SPARSE compression"
         return int(codecs.Codec.TOPK), int(_config.sparse_ratio)

@@ -4,7 +4,7 @@
 BINARY `[codes | U(N,1) | V(1,C)]` and SPARSE `[val | idx]` are single native launches; LOW_RANK / LOW_RANK_Q are in
 `lowrank.py`.  INT2 / INT4 / INT8 / IDENTITY are not slowpath wire codecs in the reference (ValueError, :80-81);
 here INT2 / INT4 / INT8 are accepted as an extension because BASELINE.json's configs use them as residual codecs, and
-INT2_MINMAX (simulation-only in the reference) as the native 4-level wire codec."""
+INT2_MINMAX (simulation-only in the reference) as the native 4-level wire codec; MXFP4 (not in the reference) is the native block-scaled codec 8."""
 from __future__ import annotations
 
 import torch
@@ -14,7 +14,7 @@ from .compress_topk import SPARSE_LAST_DIM_SIZE  # noqa: F401
 from .utils import COMPACT_COMPRESS_TYPE as T
 
 _MAP = {T.BINARY: codecs.Codec.BINARY, T.INT2: codecs.Codec.INT2, T.INT4: codecs.Codec.INT4, T.INT8: codecs.Codec.INT8,
-        T.SPARSE: codecs.Codec.TOPK, T.INT2_MINMAX: codecs.Codec.INT2_MINMAX}
+        T.SPARSE: codecs.Codec.TOPK, T.INT2_MINMAX: codecs.Codec.INT2_MINMAX, T.MXFP4: codecs.Codec.MXFP4}
 
 
 def _resolve(compress_type, rank, sparse_ratio):

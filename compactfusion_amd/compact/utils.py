@@ -22,7 +22,8 @@ ALLOW_DEPRECATED = os.environ.get("COMPACT_ALLOW_DEPRECATED", "0") == "1"
 
 class COMPACT_COMPRESS_TYPE(Enum):
     """Same members and values as the reference (utils.py:19-28), plus INT8 which the reference only has as a cache
-    quantiser (compress_quantize.py:428-484) and BASELINE.json's config 1 uses as a residual wire codec."""
+    quantiser (compress_quantize.py:428-484) and BASELINE.json's config 1 uses as a residual wire codec, and MXFP4, the block-scaled
+    OCP Microscaling codec (native codec 8), which the reference does not have."""
 
     WARMUP = "warmup"
     SPARSE = "sparse"
@@ -35,6 +36,7 @@ class COMPACT_COMPRESS_TYPE(Enum):
     LOW_RANK_Q = "low-rank-int4"
     LOW_RANK_AWL = "low-rank-awl"
     INT8 = "int8"          # extension (not in the reference enum)
+    MXFP4 = "mxfp4"        # extension (not in the reference enum)
 
 
 class CompactConfig:

@@ -3,7 +3,7 @@
 What the reference does per layer and denoise step in Python (xfuser/compact/main.py:390-420 `compact_all_gather`: compress, list
 all-gather, W decompress calls; patchpara/fwd.py:88-102; ring.py:188-206 + 265-269: compress K and V, W-1 relay hops, a
 decompress per hop) is here ONE host call into libcfx per layer: `cfx_plan_add_exchange_layer[_p2p]` replayed by `cfx_plan_run_x`
-(include/cfx.h).  For every streaming codec (1-bit, 2-bit, int4, int8, top-k, 4-level min/max) that is ONE codec launch whose reconstruction workgroups wait, state
+(include/cfx.h).  For every streaming codec (1-bit, 2-bit, int4, int8, top-k, 4-level min/max, MXFP4) that is ONE codec launch whose reconstruction workgroups wait, state
 tiles already in registers, for the packets' arrival - and in the peer-to-peer transport the exchange itself (publish this rank's word, await
 the peers') runs inside that launch; top-k and shapes without the one-launch form run the same work in stream order
 (compress ; exchange ; reconstruct) - same results, still one host call.
@@ -893,4 +893,4 @@ class LayerOp:
 def usable(cid: int, world: int, is_cuda: bool, ef: bool = True) -> bool:
     """Can the layer's exchange run as a LayerOp: a native streaming codec - or the low-rank family with error feedback -, W ranks whose
     2 (W - 1) peer tensors + own K,V fit one batch."""
-    return is_cuda and (1 <= cid <= 6 or (cid in (101, 102) and ef)) and 2 * (world - 1) + 2 <= MAX_ITEMS
+    return is_cuda and (cid in (1, 2, 3, 4, 5, 6, 8) or (cid in (101, 102) and ef)) and 2 * (world - 1) + 2 <= MAX_ITEMS

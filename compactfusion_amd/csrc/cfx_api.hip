@@ -199,6 +199,7 @@ static bool shape_ok(int codec, int N, int C, int param) {
         case CFX_CODEC_INT4: return N % 2 == 0;
         case CFX_CODEC_INT8: return true;
         case CFX_CODEC_INT2_MINMAX: return N % 4 == 0;
+        case CFX_CODEC_MXFP4: return C % 64 == 0 && param == 0;
         case CFX_CODEC_TOPK:
             return ((size_t)N * C) % 1024 == 0 && (param == 1 || param == 2 || param == 4 || param == 8 || param == 16);
         default: return false;
@@ -446,6 +447,7 @@ size_t cfx_packet_bytes(int codec, int N, int C, int param) {
         case CFX_CODEC_INT4: return n * c / 2 + 4 * c;
         case CFX_CODEC_INT8: return n * c + 4 * c;
         case CFX_CODEC_INT2_MINMAX: return n * c / 4 + 4 * c;
+        case CFX_CODEC_MXFP4: return n * c / 2 + n * c / 32;
         case CFX_CODEC_TOPK: return 2 * (n * c / param) + n * c / (2 * param);
     }
     return 0;
@@ -496,7 +498,7 @@ int cfx_i_decompress_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int para
     const int codec = codec_id(codec_arg, &bf16);
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "decompress: null ctx/items");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "decompress: batch out of range");
-    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec >= 1 && codec <= 6 ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
+    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec_known(codec) ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
     BatchD b;
     memset(&b, 0, sizeof(b));
     for (int i = 0; i < batch; ++i) {
@@ -511,6 +513,7 @@ int cfx_i_decompress_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int para
         case CFX_CODEC_INT4:
         case CFX_CODEC_INT8:
         case CFX_CODEC_INT2_MINMAX: return cfx_i_minmax_decompress(ctx, codec, N, C, batch, b, R, stream, pre, pre_val);
+        case CFX_CODEC_MXFP4: return cfx_i_mx_decompress(ctx, N, C, batch, b, stream, pre, pre_val);
         default: return cfx_i_topk_decompress(ctx, N, C, param, batch, b, stream, pre, pre_val);
     }
 }
@@ -526,7 +529,7 @@ int cfx_i_decompress2_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int par
     const int codec = codec_id(codec_arg, &bf16);
     if (!ctx || !items || !second) return fail(ctx, CFX_ERR_NULL, "decompress: null ctx/items/second");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "decompress: batch out of range");
-    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec >= 1 && codec <= 6 ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
+    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec_known(codec) ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
     if ((codec != CFX_CODEC_BINARY && codec != CFX_CODEC_INT2) || bf16)
         return fail(ctx, CFX_ERR_CODEC, "decompress: second-order states need the 1-bit or 2-bit codec, fp16");
     BatchD2 b;
@@ -614,7 +617,7 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "compress: null ctx/items");
     if (n_gated < 0 || n_gated > CFX_MAX_BATCH || (n_gated && !gated)) return fail(ctx, CFX_ERR_BATCH, "compress: gated batch out of range");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "compress: batch out of range");
-    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec >= 1 && codec <= 6 ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "compress: bad codec/shape");
+    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec_known(codec) ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "compress: bad codec/shape");
     if (n_ride < 0 || n_ride > CFX_MAX_BATCH || (n_ride && !ride)) return fail(ctx, CFX_ERR_BATCH, "compress: ride-along batch out of range");
     if (n_ride && codec != CFX_CODEC_BINARY) return fail(ctx, CFX_ERR_CODEC, "compress: ride-along reconstruction items need the 1-bit codec");
     // second-order states (include/cfx.h, "Second-order residual"): the 1-bit and 2-bit codecs, fp16, error feedback on, no layer form
@@ -675,6 +678,7 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     cc.fused = false; cc.tick = nullptr; cc.slot = 0; cc.stream_cus = 0; cc.R = cc.P = 0;
     cc.second = second; cc.decay = decay;
     if (codec == CFX_CODEC_TOPK) return cfx_i_topk_compress(cc);
+    if (codec == CFX_CODEC_MXFP4) return cfx_i_mx_compress(cc);
 
     // statistics + finalize: ONE launch with the in-launch finalize (default), or the two-kernel sequence
     const bool fused = ctx->fused && CB <= TICK_MAX_CB;
@@ -775,7 +779,7 @@ bool cfx_i_shape_ok(int codec, int N, int C, int param) { return shape_ok(codec,
 // The 2-bit layer launch takes the external gate too (k_int2_compress_gated's group D).  With the exchange as a one-wave kernel on an exchange
 // stream it measured 2.40-2.46 ms per FLUX step against 2.03 for three launches in stream order - a resident polling kernel on another queue
 // alone costs that launch 4 us per layer (tools/xgate_probe.py, kind gated+poller) -; with the exchange INSIDE the launch (P2PInline) 2.11.
-bool cfx_i_has_xlayer_form(int codec) { return (codec & 0xff) >= CFX_CODEC_BINARY && (codec & 0xff) <= CFX_CODEC_INT2_MINMAX; }
+bool cfx_i_has_xlayer_form(int codec) { return codec_known(codec & 0xff); }
 unsigned* cfx_i_ticket_block(cfx_ctx* ctx, void* stream) {
     if (!ctx->tick && cfx_prepare(ctx) != CFX_OK) return nullptr;
     return ctx->tick + (size_t)ticket_slot(ctx, stream) * CFX_MAX_BATCH * TICK_WORDS;

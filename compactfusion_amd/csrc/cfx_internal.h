@@ -180,6 +180,9 @@ static inline int codec_id(int codec_arg, bool* bf16) {
     return id;
 }
 
+// the streaming codecs' ids (include/cfx.h enum cfx_codec; 7 is not one)
+static inline bool codec_known(int id) { return (id >= CFX_CODEC_BINARY && id <= CFX_CODEC_INT2_MINMAX) || id == CFX_CODEC_MXFP4; }
+
 // ---------------------------------------------------------------------------------------------------
 // Plan / communicator internals, shared by cfx_absmean.hip (the fused pipeline launch) and cfx_plan.hip (everything else)
 // ---------------------------------------------------------------------------------------------------

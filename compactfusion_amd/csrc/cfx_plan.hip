@@ -313,7 +313,7 @@ static int add_exchange_layer(cfx_plan* p, int codec, int N, int C, int param, i
     if (!p) return CFX_ERR_NULL;
     if (n_recon < 1 || n_recon > CFX_MAX_BATCH || !recon) return fail(p->ctx, CFX_ERR_BATCH, "plan: exchange layer needs 1..CFX_MAX_BATCH reconstruction items");
     bool bf16 = false;
-    if (!codec_id(codec, &bf16) || (codec & 0xff) > CFX_CODEC_INT2_MINMAX) return fail(p->ctx, CFX_ERR_CODEC, "plan: exchange layer: unknown codec");
+    if (!codec_known(codec_id(codec, &bf16))) return fail(p->ctx, CFX_ERR_CODEC, "plan: exchange layer: unknown codec");
     if (comm && (!send || !recv)) return fail(p->ctx, CFX_ERR_NULL, "plan: exchange layer: null send/recv");
     if (!p->side && need_side) {
         // the flag kernels poll: they need a hardware queue of their own (cfx.h, exchange lane) - a CU-masked stream has one

@@ -35,6 +35,8 @@
  *   INT2_MINMAX [ codes N*C/4 B : byte [n/4][c] = q[n][c] | q[n+1][c]<<2 | q[n+2][c]<<4 | q[n+3][c]<<6 | scale C fp16 | min C fp16 ]
  *           (no wire in the reference, which only simulates it: compress_quantize.py:386-426; INT4's row-per-byte convention, four rows)
  *   TOPK    [ val N*C/m fp16 | idx N*C/(2m) B : (i1<<4)|i2 per 2m-block of the flat (-1,1024) view ]           slowpath.py:76-79
+ *   MXFP4   [ codes N*C/2 B : byte [n][j] = code[n][2j] | code[n][2j+1] << 4 | scale N*C/32 B : one E8M0 byte per block, row-major ]
+ *           (no wire in the reference: the OCP Microscaling format, blocks of 32 consecutive elements of a row)
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
  *   and N odd, int4 with C % 16 == 8 and N/2 odd, INT2_MINMAX with C % 16 == 8 and N/4 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
  *   INT4 `min` of a channel whose minimum is zero: where zeros of BOTH signs occur among the channel's deltas, `min` may hold either zero
@@ -57,6 +59,29 @@
  *   INT4's kernel ids (cfx_profile_enable).  Ride-along reconstruction items (cfx_compress_batch_ex, n_ride > 0) stay the 1-bit codec's:
  *   with codec 6, as with INT4, they are CFX_ERR_CODEC.
  *
+ * MXFP4 (CFX_CODEC_MXFP4 = 8, param 0; any other param: CFX_ERR_SHAPE, sizes 0): the OCP Microscaling (MX v1.0) conversion - floor
+ *   scale, round-to-nearest-even elements, saturation - with a lower clamp on the shared exponent so that decode never leaves fp16.
+ *   Blocks are 32 consecutive elements of a row (C % 32 == 0: also blocks of the flat view, never straddling rows); a block's scale is
+ *   a function of that block alone, so the codec is one streaming pass with nothing global to wait for.  Bit for bit, one fp16 rounding
+ *   per line:
+ *       d      = fp16(x - base)                                   (base NULL: x)
+ *       a      = max over the block of (bits(d) & 0x7fff)         (integer max: the largest magnitude)
+ *       a >= 0x7c00 (a NaN or an inf in the block): scale byte 0xFF, all 16 code bytes 0, every element of the block reconstructs to a NaN
+ *       e      = max( floor(log2 |d|max), -21 )                   (normal: (a >> 10) - 15; subnormal: from the leading bit; a == 0 gives -21)
+ *       X      = e - 2            scale byte = X + 127            (so X in [-23, 13], bytes 104 ... 140)
+ *       y      = |d| / 2^X                                         (exact; y < 8 by construction)
+ *       mag    = index of the grid point {0, 0.5, 1, 1.5, 2, 3, 4, 6} nearest to y; a tie goes to the EVEN index; y > 6 saturates to index 7
+ *       code   = (sign bit of d) << 3 | mag                        (a negative delta that rounds to magnitude 0 keeps its sign bit: code 8)
+ *       recv   = (+-) grid[mag] * 2^X                              (exactly representable in fp16: that is what the clamp at -21 buys; |recv| <= 49152)
+ *       new_base = recon = fp16(base + recv)                       (base NULL: recv;  CFX_FLAG_NO_EF: new_base = x)
+ *   Shapes: C % 64 == 0, any N >= 1 (the packet length is even and every section a whole number of 32-bit words); cfx_packet_bytes =
+ *   N*C/2 + N*C/32 (4.25 bits per element); cfx_workspace_bytes is 0, as for top-k: callers pass NULL / 0.  Forms: stand-alone compress /
+ *   decompress (they report top-k's kernel ids, 13 and 14) and the one-launch layer k_mx_layer (the gated layer id, 31), taken under
+ *   k_topk_layer's conditions - gated items, cfx_set_gated_launch on, no capture, a stream of >= 128 CUs, loop-back items reading this
+ *   launch's packets; otherwise, and under stream capture, compress ; (exchange) ; decompress in stream order with the same results.
+ *   Refused, as for INT4: CFX_ELEM_BF16 (CFX_ERR_CODEC, sizes 0), the second-order entry points and cfx_plan_set_second_order
+ *   (CFX_ERR_CODEC: residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items (CFX_ERR_CODEC).  Id 7 is no codec.
+ *
  * bf16 activations (CFX_CODEC_BINARY and CFX_CODEC_INT2 only)
  *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,
  *   cfx_compress[_batch[_ex|_gated]], cfx_decompress[_batch], cfx_plan_add_compress[_ex|_gated], cfx_plan_add_decompress,
@@ -71,7 +96,7 @@
  *   Packet layout, cfx_packet_bytes and cfx_workspace_bytes are those of the fp16 codec: a bf16 sender's packet is a valid fp16-path
  *   packet (a receiver may reconstruct it onto an fp16 state with the plain codec id, and the other way round).  Domain as for the
  *   fp16 path: finite inputs with |x - base| < 65504; outside it the result is unspecified (see "Non-finite input").
- *   The bit on codecs 3 - 6, and any other bit above the codec id, is CFX_ERR_CODEC; the sizes of such a codec argument are 0.
+ *   The bit on codecs 3 - 6 and 8, and any other bit above the codec id, is CFX_ERR_CODEC; the sizes of such a codec argument are 0.
  *   Every form the fp16 path has exists for bf16 (stand-alone, in-launch finalize, ride-along, one-launch layer forms, the peer-to-peer
  *   exchange inside the launch), with the documented fall-backs; cfx_plan_run_pipelined and the rank-K 1-bit codec are fp16 only (a
  *   pipelined replay of bf16 ops runs as cfx_plan_run).
@@ -91,13 +116,14 @@
  *   In place is allowed: new_base == base, new_delta_base == delta_base.  base and delta_base are required (CFX_ERR_NULL); a
  *   reconstruction item may have new_delta_base NULL (update_cache = False: recon only); a compress item needs new_base and
  *   new_delta_base with CFX_FLAG_UPDATE_CACHE and writes only the packet without it.  CFX_ERR_CODEC before any launch: CFX_FLAG_NO_EF
- *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6 (those compose cfx_residual2_delta / _update
+ *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6 and 8 (those compose cfx_residual2_delta / _update
  *   around the codec).  The second-order launches report the kernel ids of their first-order twins (cfx_profile_enable).
  *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
  *   INT4 / INT8 / INT2_MINMAX: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
  *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
  *   TOPK:        |delta| is ranked as the reference's tl.argmax ranks it: NaN above everything, +inf included; the first NaN wins.
+ *   MXFP4:       a block with a NaN or an inf delta is the 0xFF block above (codes 0, NaN reconstruction); its neighbours are untouched.
  *   BINARY / INT2: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
  *                NaN; the outputs are finite garbage or NaN, and need not match the reference.
  */
@@ -136,7 +162,8 @@ enum cfx_codec {
     CFX_CODEC_INT4 = 3,      /* per-channel min/max 16 levels, rows paired per byte */
     CFX_CODEC_INT8 = 4,      /* per-channel affine int8, zero point int16 */
     CFX_CODEC_TOPK = 5,      /* COMPACT_COMPRESS_TYPE.SPARSE, param = m in {1,2,4,8,16} */
-    CFX_CODEC_INT2_MINMAX = 6 /* COMPACT_COMPRESS_TYPE.INT2_MINMAX: per-channel min/max 4 levels, four rows per byte; param 0 */
+    CFX_CODEC_INT2_MINMAX = 6, /* COMPACT_COMPRESS_TYPE.INT2_MINMAX: per-channel min/max 4 levels, four rows per byte; param 0 */
+    CFX_CODEC_MXFP4 = 8      /* COMPACT_COMPRESS_TYPE.MXFP4: FP4 E2M1 elements, one E8M0 scale per 32 of a row; param 0 (7 is no codec) */
 };
 /* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit and 2-bit codecs; "bf16 activations" above) */
 #define CFX_ELEM_BF16 0x100

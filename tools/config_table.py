@@ -40,10 +40,13 @@ CONFIGS = [
     ("6c FLUX.1 1024^2 ring 8, INT2_MINMAX (config 3's shard)", 6, 0, (544, 3072), 57, 2, 14, True),
     ("7a FLUX.1 1024^2 ring 8, INT2 (config 3's shard)", 2, 0, (544, 3072), 57, 2, 14, True),
     ("7b FLUX.1 1024^2 ring 8, INT4 (config 3's shard)", 3, 0, (544, 3072), 57, 2, 14, True),
+    # the block-scaled MXFP4 codec (codec 8): no statistic to wait for (no C restatement: the check column is n/a)
+    ("8a PixArt-a 512^2 SP2 patch-gather MXFP4 (config 2's shard)", 8, 0, (1024, 1152), 28, 2, 4, False),
+    ("8c FLUX.1 1024^2 ring 8, MXFP4 (config 3's shard)", 8, 0, (544, 3072), 57, 2, 14, True),
 ]
 NAMES = {1: "binary", 2: "int2", 3: "int4", 4: "int8", 5: "topk"}
 # algorithmic bytes per element (compress + error feedback, reconstruct); low-rank: x + state in, state out (6), state in / out (4)
-ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8), 6: (6.25, 4.25), 101: (6.0, 4.0)}
+ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8), 6: (6.25, 4.25), 8: (6.53125, 4.53125), 101: (6.0, 4.0)}
 
 
 def alg_bytes(cid, N, C, L, ncomp, nrec, update):
@@ -175,7 +178,7 @@ def gpu_step(cid, param, N, C, L, ncomp, nrec, update, min_steps=20, budget_s=0.
 
 
 def cpu_step(cid, param, N, C, L, ncomp, nrec, update, budget=8.0):
-    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX
+    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4
         return None, 0
     from oracle import c_oracle as CO
     name = NAMES[cid]
