@@ -171,6 +171,31 @@ def sim_mxfp4(input_tensor: torch.Tensor):
     return dequantize_mxfp4(*quantize_mxfp4(input_tensor))
 
 
+# ---- BINARY_BLOCK (extension: not in the reference; include/cfx.h "BINARY_BLOCK") -----------------------------------
+def quantize_binary_block(input_tensor: torch.Tensor, block: int = 64):
+    """-> bits (N, C/8) uint8 [bit i of byte [n][j] = x[n][8j+i] >= 0], scales (N, C/block) fp16 [the abs-mean of each block of `block`
+    consecutive elements of a row].  The native BINARY_BLOCK wire codec at residual 0."""
+    x = _nc(input_tensor)
+    N, C = x.shape
+    assert block in (32, 64, 128), f"block size must be 32, 64 or 128, got {block}"
+    assert C % max(block, 64) == 0, f"Dimension C (1) size must be a multiple of {max(block, 64)} for blocks of {block}, got {C}"
+    pkt, _ = codecs.compress(K.BINARY_BLOCK, x, None, N, C, block, update_cache=False)
+    return pkt[:N * C // 16].view(torch.uint8).view(N, C // 8), pkt[N * C // 16:].view(N, C // block)
+
+
+def dequantize_binary_block(bits: torch.Tensor, scales: torch.Tensor):
+    assert bits.dtype == torch.uint8 and scales.dtype == torch.half
+    N, C8 = bits.shape
+    C = C8 * 8
+    block = C // scales.shape[1]
+    assert scales.shape[0] == N and block in (32, 64, 128) and scales.shape[1] * block == C
+    return codecs.decompress(K.BINARY_BLOCK, _cat_packet(bits, scales), None, N, C, block)
+
+
+def sim_binary_block(input_tensor: torch.Tensor, block: int = 64):
+    return dequantize_binary_block(*quantize_binary_block(input_tensor, block))
+
+
 def sim_int4(input_tensor: torch.Tensor, dim):
     x = _nc(input_tensor)
     if dim == 1:

@@ -20,6 +20,10 @@ _CODECS = {
     "lowrank12": (T.LOW_RANK, 12, False),
     "lowrank16": (T.LOW_RANK, 16, False),                        # defined upstream, commented out of its dispatcher (:22-23)
     "lowrankq32": (T.LOW_RANK_Q, 32, False),
+    # extension (not in the reference): the block-scaled 1-bit codec; the preset also sets the block size switch (configure(binary_block=B))
+    "binblock32": (T.BINARY_BLOCK, -1, False),
+    "binblock64": (T.BINARY_BLOCK, -1, False),
+    "binblock128": (T.BINARY_BLOCK, -1, False),
 }
 # method -> PatchConfig arguments (use_compact, async_comm, async_warmup = the warm-up steps unless given)     configs.py:110-165
 _PATCH = {"int2patch": (True, False, None), "df": (False, True, None), "patch": (False, False, 0)}
@@ -45,6 +49,9 @@ def get_config(model_name: str, method: str) -> CompactConfig:
         return CompactConfig(enabled=False, compress_func=None, simulate=False, log_stats=False)
     if method in _CODECS:
         codec, rank, fast = _CODECS[method]
+        if codec == T.BINARY_BLOCK:
+            from .. import config
+            config.configure(binary_block=int(method[len("binblock"):]))
         return CompactConfig(enabled=True, compress_func=_schedule(codec, warmup), comp_rank=rank, residual=1, ef=True, simulate=False,
                              log_stats=False, fastpath=fast)
     if method in _PATCH:

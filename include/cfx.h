@@ -37,6 +37,8 @@
  *   TOPK    [ val N*C/m fp16 | idx N*C/(2m) B : (i1<<4)|i2 per 2m-block of the flat (-1,1024) view ]           slowpath.py:76-79
  *   MXFP4   [ codes N*C/2 B : byte [n][j] = code[n][2j] | code[n][2j+1] << 4 | scale N*C/32 B : one E8M0 byte per block, row-major ]
  *           (no wire in the reference: the OCP Microscaling format, blocks of 32 consecutive elements of a row)
+ *   BINARY_BLOCK [ bits N*C/8 B : bit i of byte j of row n = d[n,8j+i] >= 0 (BINARY's bit layout) | scale N*C/B fp16 : row-major, one per block ]
+ *           (no wire in the reference: the block-wise sign compressor of 1-bit Adam / block signSGD, B = param consecutive elements of a row)
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
  *   and N odd, int4 with C % 16 == 8 and N/2 odd, INT2_MINMAX with C % 16 == 8 and N/4 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
  *   INT4 `min` of a channel whose minimum is zero: where zeros of BOTH signs occur among the channel's deltas, `min` may hold either zero
@@ -82,7 +84,26 @@
  *   Refused, as for INT4: CFX_ELEM_BF16 (CFX_ERR_CODEC, sizes 0), the second-order entry points and cfx_plan_set_second_order
  *   (CFX_ERR_CODEC: residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items (CFX_ERR_CODEC).  Id 7 is no codec.
  *
- * bf16 activations (CFX_CODEC_BINARY and CFX_CODEC_INT2 only)
+ * BINARY_BLOCK (CFX_CODEC_BINARY_BLOCK = 10, param = the block size B in {32, 64, 128}; any other param: CFX_ERR_SHAPE, sizes 0): sign
+ *   bits plus one fp16 abs-mean per block of B consecutive elements of a row.  A block's scale is a function of that block alone, so -
+ *   unlike BINARY's rank-1 scales - the codec is one streaming pass with nothing global to wait for.  Bit for bit:
+ *       d        = fp16(x - base)                                 (base NULL: x)
+ *       bit      = d >= 0                                         (-0 gives 1; a NaN would give 0)
+ *       s        = fp16( fp32(exact sum of |d| over the block, in units of 2^-24) / fp32(B) )
+ *                  (mean16 of the sum of habs_units, cfx_device.h; mean16_exact of oracle/ref_np.py; the sum is exact: order-independent)
+ *       recv     = bit ? s : -s                                   (s == 0: +0 / -0; |recv| <= 65504 always: a mean never exceeds its maximum)
+ *       new_base = recon = fp16(base + recv)                      (base NULL: recv, bits verbatim;  CFX_FLAG_NO_EF: new_base = x)
+ *   Shapes: C % max(B, 64) == 0, any N >= 1 (blocks never straddle rows, the bit section is a whole number of 64-bit words, the packet
+ *   has an even number of halves); cfx_packet_bytes = N*C/8 + 2*N*C/B (1.5 / 1.25 / 1.125 bits per element); cfx_workspace_bytes is 0, as
+ *   for top-k and MXFP4: callers pass NULL / 0.  CFX_ELEM_BF16 is accepted (codec argument 0x10A) under the "bf16 activations" rules below.
+ *   Forms: stand-alone compress / decompress (they report top-k's kernel ids, 13 and 14) and the one-launch layer k_bb_layer (the gated
+ *   layer id, 31), taken under k_mx_layer's conditions - gated items, cfx_set_gated_launch on, no capture, a stream of >= 128 CUs,
+ *   loop-back items reading this launch's packets; otherwise, and under stream capture, compress ; (exchange) ; decompress in stream
+ *   order with the same results.  Refused, as for MXFP4: the second-order entry points and cfx_plan_set_second_order (CFX_ERR_CODEC:
+ *   residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items (CFX_ERR_CODEC), any other high bit on the
+ *   codec argument (CFX_ERR_CODEC, sizes 0).  Id 9 is no codec.
+ *
+ * bf16 activations (CFX_CODEC_BINARY, CFX_CODEC_INT2 and CFX_CODEC_BINARY_BLOCK only)
  *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,
  *   cfx_compress[_batch[_ex|_gated]], cfx_decompress[_batch], cfx_plan_add_compress[_ex|_gated], cfx_plan_add_decompress,
  *   cfx_plan_add_exchange_layer[_p2p], and through them cfx_plan_copy_op) says that ALL tensor operands of the call - x, base, new_base,
@@ -90,7 +111,7 @@
  *   CFX_FLAG_ELEM_BF16 in `flags`.  The residual domain and the wire stay fp16:
  *       d        = fp16_rne( fp32(x) - fp32(base) )          one fp32 subtraction, one rounding to fp16; base NULL: d = fp16_rne(fp32(x))
  *       d -> recv  exactly the fp16 path: sign bits / 2-bit codes, exact sums in units of 2^-24, fp16 scales, packet bytes;
- *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels, in fp16
+ *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels  or +-s of the block (BINARY_BLOCK), in fp16
  *       new_base = recon = bf16_rne( fp32(base) + fp32(recv) )     base NULL: bf16_rne(fp32(recv))
  *       CFX_FLAG_NO_EF: new_base = x, copied verbatim as bf16 bits
  *   Packet layout, cfx_packet_bytes and cfx_workspace_bytes are those of the fp16 codec: a bf16 sender's packet is a valid fp16-path
@@ -116,7 +137,7 @@
  *   In place is allowed: new_base == base, new_delta_base == delta_base.  base and delta_base are required (CFX_ERR_NULL); a
  *   reconstruction item may have new_delta_base NULL (update_cache = False: recon only); a compress item needs new_base and
  *   new_delta_base with CFX_FLAG_UPDATE_CACHE and writes only the packet without it.  CFX_ERR_CODEC before any launch: CFX_FLAG_NO_EF
- *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6 and 8 (those compose cfx_residual2_delta / _update
+ *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6, 8 and 10 (those compose cfx_residual2_delta / _update
  *   around the codec).  The second-order launches report the kernel ids of their first-order twins (cfx_profile_enable).
  *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
@@ -124,7 +145,7 @@
  *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
  *   TOPK:        |delta| is ranked as the reference's tl.argmax ranks it: NaN above everything, +inf included; the first NaN wins.
  *   MXFP4:       a block with a NaN or an inf delta is the 0xFF block above (codes 0, NaN reconstruction); its neighbours are untouched.
- *   BINARY / INT2: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
+ *   BINARY / INT2 / BINARY_BLOCK: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
  *                NaN; the outputs are finite garbage or NaN, and need not match the reference.
  */
 #ifndef CFX_H
@@ -163,9 +184,10 @@ enum cfx_codec {
     CFX_CODEC_INT8 = 4,      /* per-channel affine int8, zero point int16 */
     CFX_CODEC_TOPK = 5,      /* COMPACT_COMPRESS_TYPE.SPARSE, param = m in {1,2,4,8,16} */
     CFX_CODEC_INT2_MINMAX = 6, /* COMPACT_COMPRESS_TYPE.INT2_MINMAX: per-channel min/max 4 levels, four rows per byte; param 0 */
-    CFX_CODEC_MXFP4 = 8      /* COMPACT_COMPRESS_TYPE.MXFP4: FP4 E2M1 elements, one E8M0 scale per 32 of a row; param 0 (7 is no codec) */
+    CFX_CODEC_MXFP4 = 8,     /* COMPACT_COMPRESS_TYPE.MXFP4: FP4 E2M1 elements, one E8M0 scale per 32 of a row; param 0 (7 is no codec) */
+    CFX_CODEC_BINARY_BLOCK = 10 /* COMPACT_COMPRESS_TYPE.BINARY_BLOCK: sign bits, one fp16 abs-mean per param = 32 / 64 / 128 of a row (9 is no codec) */
 };
-/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit and 2-bit codecs; "bf16 activations" above) */
+/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit, 2-bit and block-scaled 1-bit codecs; "bf16 activations" above) */
 #define CFX_ELEM_BF16 0x100
 
 enum cfx_flags {

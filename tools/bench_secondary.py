@@ -126,7 +126,7 @@ def configs_leg(out, hbm_peak_gbs):
         cfgs = {}
         for name, cid_, param_, (n_, c_), l_, ncomp, nrec, upd in CT.CONFIGS:
             ms_ = CT.gpu_step(cid_, param_, n_, c_, l_, ncomp, nrec, upd, min_steps=8, budget_s=0.05)
-            ab = CT.alg_bytes(cid_, n_, c_, l_, ncomp, nrec, upd)
+            ab = CT.alg_bytes(cid_, n_, c_, l_, ncomp, nrec, upd, param_)
             key = name.split()[0] + (" " + " ".join(name.split()[-2:]) if name.startswith("5") else "")
             cfgs[key] = {"workload": name, "shard": [n_, c_], "layers": l_, "ms_per_step": round(ms_, 4), "alg_bytes": ab,
                          "frac": round(ab / (ms_ * 1e-3) / 1e9 / hbm_peak_gbs, 4)}

@@ -14,8 +14,8 @@ import torch
 
 from compactfusion_amd import _lib, codecs as K
 
-ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8)}
-NAMES = {1: "1-bit", 2: "2-bit", 3: "int4", 4: "int8", 5: "top-k 1:8"}
+ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8), 10: (6.125 + 2.0 / 64, 4.125 + 2.0 / 64)}
+NAMES = {1: "1-bit", 2: "2-bit", 3: "int4", 4: "int8", 5: "top-k 1:8", 10: "1-bit, blocks of 64"}
 SHAPES = [("S1 config 1: [1,4096,1152]", 4096, 1152), ("S2 PixArt-a 512^2 SP2", 1024, 1152), ("S3 FLUX 1024^2 ring 8", 544, 3072),
           ("S4 CogVideoX-5B SP4", 4448, 3072), ("S5 SD3 1024^2 SP8", 512, 1536)]
 
@@ -32,8 +32,8 @@ def main():
         g = torch.Generator(device=dev).manual_seed(0)
         xb = [torch.randn(14, N, C, generator=g, device=dev).half() for _ in range(S)]
         xx = [(b[:2].float() + 0.1 * torch.randn(2, N, C, generator=g, device=dev)).half() for b in xb]
-        for cid in (1, 2, 3, 4, 5):
-            param = 8 if cid == 5 else 0
+        for cid in (1, 2, 3, 4, 5, 10):
+            param = 8 if cid == 5 else (64 if cid == 10 else 0)
             if cid == 5 and (N * C) % 1024:
                 continue
             slot = (K.packet_bytes(cid, N, C, param) + 255) // 256 * 256

@@ -43,16 +43,35 @@ CONFIGS = [
     # the block-scaled MXFP4 codec (codec 8): no statistic to wait for (no C restatement: the check column is n/a)
     ("8a PixArt-a 512^2 SP2 patch-gather MXFP4 (config 2's shard)", 8, 0, (1024, 1152), 28, 2, 4, False),
     ("8c FLUX.1 1024^2 ring 8, MXFP4 (config 3's shard)", 8, 0, (544, 3072), 57, 2, 14, True),
+    # the block-scaled 1-bit codec (codec 10, param = the block size; 0x10A: bf16 activations and states): no statistic to wait for either
+    ("9a FLUX.1 1024^2 ring 8, BINARY_BLOCK B=32 (config 3's shard)", 10, 32, (544, 3072), 57, 2, 14, True),
+    ("9b FLUX.1 1024^2 ring 8, BINARY_BLOCK B=64 (config 3's shard)", 10, 64, (544, 3072), 57, 2, 14, True),
+    ("9c FLUX.1 1024^2 ring 8, BINARY_BLOCK B=128 (config 3's shard)", 10, 128, (544, 3072), 57, 2, 14, True),
+    ("9d FLUX.1 1024^2 ring 8, BINARY_BLOCK B=32 bf16 (config 3's shard)", 0x10A, 32, (544, 3072), 57, 2, 14, True),
+    ("9e FLUX.1 1024^2 ring 8, BINARY_BLOCK B=64 bf16 (config 3's shard)", 0x10A, 64, (544, 3072), 57, 2, 14, True),
+    ("9f FLUX.1 1024^2 ring 8, BINARY_BLOCK B=128 bf16 (config 3's shard)", 0x10A, 128, (544, 3072), 57, 2, 14, True),
+    ("9g PixArt-a 512^2 SP2 patch-gather BINARY_BLOCK B=64 (config 2's shard)", 10, 64, (1024, 1152), 28, 2, 4, False),
+    ("9h CogVideoX-5B SP4 ring BINARY_BLOCK B=64 (config 4's shard)", 10, 64, (4448, 3072), 42, 2, 6, True),
+    ("9i SD3 1024^2 SP8 patch-gather BINARY_BLOCK B=64 (config 5's shard)", 10, 64, (512, 1536), 24, 2, 16, False),
+    ("9j FLUX.1 1024^2 ring 8, 1-bit bf16 (config 3's shard)", 0x101, 0, (544, 3072), 57, 2, 14, True),
 ]
 NAMES = {1: "binary", 2: "int2", 3: "int4", 4: "int8", 5: "topk"}
 # algorithmic bytes per element (compress + error feedback, reconstruct); low-rank: x + state in, state out (6), state in / out (4)
 ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 + 2.5 / 8, 4 + 2.5 / 8), 6: (6.25, 4.25), 8: (6.53125, 4.53125), 101: (6.0, 4.0)}
 
 
-def alg_bytes(cid, N, C, L, ncomp, nrec, update):
+def alg_pair(cid, param=0):
+    """(compress + error feedback, reconstruct) bytes per element of a codec argument; the block-scaled 1-bit codec: 1/8 + 2/B of packet"""
+    cid &= 0xff
+    if cid == 10:
+        return 6 + 0.125 + 2.0 / param, 4 + 0.125 + 2.0 / param
+    return ALG[cid]
+
+
+def alg_bytes(cid, N, C, L, ncomp, nrec, update, param=0):
     """Algorithmic HBM bytes of one step: `ncomp` tensors compressed (+ error feedback when the compress updates the state; a compress
     that does not - gather mode - reads x and the state and writes the packet only: 2 B/el less) and `nrec` reconstructed, per layer."""
-    c, d = ALG[cid]
+    c, d = alg_pair(cid, param)
     return int(L * N * C * (ncomp * (c if update else c - 2.0) + nrec * d))
 
 
@@ -79,10 +98,11 @@ def gpu_step(cid, param, N, C, L, ncomp, nrec, update, min_steps=20, budget_s=0.
     # synthetic data as bench.py's: states that track their activations, the step-to-step drift 0.1 of the activations' scale (independent
     # random states would be residuals of |d| ~ 1.1 - at that size the 1-bit / 2-bit codecs' row partials (512 channels) leave their 32-bit
     # words and every U job takes a second round trip for the 64-bit ones: 1.61 instead of 1.45 ms per step at config 3)
-    own = torch.randn(Lb, ncomp, N, C, generator=g, device=dev).half()
-    x = [(own.float() + 0.1 * torch.randn(Lb, ncomp, N, C, generator=g, device=dev)).half() for _ in range(2)]
-    peers = torch.randn(Lb, nrec, N, C, generator=g, device=dev).half()
-    lowrank = cid >= 100
+    lowrank = 100 <= cid < 0x100
+    dt = torch.bfloat16 if cid & 0x100 else torch.float16          # (CFX_ELEM_BF16 on the codec argument: bf16 activations and states)
+    own = torch.randn(Lb, ncomp, N, C, generator=g, device=dev).to(dt)
+    x = [(own.float() + 0.1 * torch.randn(Lb, ncomp, N, C, generator=g, device=dev)).to(dt) for _ in range(2)]
+    peers = torch.randn(Lb, nrec, N, C, generator=g, device=dev).to(dt)
     run_stream = _streams(ctx, lib)[0]
     sh = run_stream.cuda_stream
     if not lowrank:
@@ -178,7 +198,7 @@ def gpu_step(cid, param, N, C, L, ncomp, nrec, update, min_steps=20, budget_s=0.
 
 
 def cpu_step(cid, param, N, C, L, ncomp, nrec, update, budget=8.0):
-    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4
+    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4, BINARY_BLOCK, bf16
         return None, 0
     from oracle import c_oracle as CO
     name = NAMES[cid]
