@@ -37,7 +37,8 @@ def needs_build(lib: str = LIB) -> bool:
         return True
     t = os.path.getmtime(lib)
     deps = SRC + [os.path.join(INC, "cfx.h"), os.path.join(INC, "cfx_dev.h"), os.path.join(PKG_DIR, "csrc", "cfx_internal.h"),
-                  os.path.join(PKG_DIR, "csrc", "cfx_lr.h"), os.path.join(PKG_DIR, "csrc", "cfx_device.h"), os.path.join(PKG_DIR, "csrc", "cfx_host.h")]
+                  os.path.join(PKG_DIR, "csrc", "cfx_lr.h"), os.path.join(PKG_DIR, "csrc", "cfx_device.h"), os.path.join(PKG_DIR, "csrc", "cfx_host.h"),
+                  os.path.join(PKG_DIR, "csrc", "cfx_local.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1,4 +1,4 @@
-// Device code shared by the codec families of libcfx.so (cfx_absmean.hip, cfx_minmax.hip, cfx_topk.hip, cfx_api.hip): element types, loads /
+// Device code shared by the codec families of libcfx.so (cfx_absmean.hip, cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip, cfx_api.hip): element types, loads /
 // stores, the tagged-word arenas, tile coordinates, the ticket / gate geometry and the in-launch waits, the peer-to-peer exchange a layer
 // launch runs inside itself.  (Round 6: cfx_kernels.hip was one 4 130-line translation unit; it is now this header + one file per family
 // + the C-ABI.)
@@ -100,6 +100,9 @@ __device__ __forceinline__ void st_wt(u16* p, u16 v) { __hip_atomic_store(p, v, 
 __device__ __forceinline__ u16 ld_wt(const u16* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned char ld_wt(const unsigned char* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_wt(unsigned char* p, unsigned char v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// a packet word that workgroups of the same launch read (WT: a layer launch) or only later launches do (a plain store)
+template <bool WT, class T, class V>
+__device__ __forceinline__ void st_put(T* p, V v) { if constexpr (WT) st_wt(p, (T)v); else *p = (T)v; }
 // system scope: the word may live in ANOTHER GPU's memory (packets read in place through an IPC mapping, cfx_plan_add_exchange_layer_p2p)
 __device__ __forceinline__ u64 ld_sys(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ unsigned ld_sys(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }

@@ -1,5 +1,6 @@
 // Host-side internals shared by the translation units of libcfx.so's streaming codecs (cfx_api.hip: context, C-ABI, dispatch; cfx_absmean.hip,
-// cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip: each family's kernels AND the code that launches them).  Not part of the ABI.
+// cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip: each family's kernels AND the code that launches them; cfx_local.h: the launch
+// skeleton the last three - the block-local codecs - share).  Not part of the ABI.
 #ifndef CFX_HOST_H
 #define CFX_HOST_H
 #include "cfx_device.h"
@@ -51,6 +52,12 @@ CFX_HIDDEN int cfx_i_decompress_checked(cfx_ctx* ctx, int codec, int N, int C, i
 CFX_HIDDEN int cfx_i_decompress2_checked(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items,
                                          const cfx_second_item* second, float decay, void* stream, unsigned* pre, unsigned pre_val);
 }  // extern "C"
+// cfx_local.h (inline: the block-local families' files include it): the stand-alone kernels' grid, the layer form of a compress call
+// (> 0: `a` filled and the gates booked, the grid of k_*_layer; 0: none; < 0: an error code), the tail behind a stand-alone compress launch
+struct LocalLayerArgs;
+CFX_HIDDEN dim3 cfx_i_local_grid(int N, int C, int batch);
+CFX_HIDDEN int cfx_i_local_layer(CompressCall& cc, LocalLayerArgs& a);
+CFX_HIDDEN int cfx_i_local_tail(CompressCall& cc, const char* what);
 // (short names the family files were written with)
 #define auto_rows cfx_i_auto_rows
 #define fused_rows cfx_i_fused_rows

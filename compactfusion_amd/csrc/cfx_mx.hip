@@ -1,7 +1,7 @@
 // libcfx.so - the MXFP4 block-scaled residual codec (CFX_CODEC_MXFP4, include/cfx.h "MXFP4"): 32 consecutive elements share one E8M0
 // power-of-two scale, every element is an FP4 E2M1 value.  A block's scale is a function of the block alone, so - as for top-k - there is
-// nothing global to wait for: compress / decompress kernels and the layer launch (k_mx_layer), the shape of cfx_topk.hip.
-// Shared device code: cfx_device.h; the C-ABI and the dispatch: cfx_api.hip.
+// nothing global to wait for: compress / decompress kernels and the layer launch (k_mx_layer) are cfx_local.h's skeleton around this codec.
+// Shared device code: cfx_device.h; the launch skeleton of the block-local codecs: cfx_local.h; the C-ABI and the dispatch: cfx_api.hip.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -13,6 +13,7 @@
 #include "cfx_internal.h"
 #include "cfx_device.h"
 #include "cfx_host.h"
+#include "cfx_local.h"
 
 // ---------------------------------------------------------------------------------------------------
 // One lane owns 8 consecutive flat elements (one 16-byte load of x, one of base, one 32-bit word of codes); a block is the 4 lanes of a
@@ -20,7 +21,6 @@
 // integer / exact fp32 arithmetic, not with v_cvt_scalef32_pk_fp4_f16 / _pk_f16_fp4: the contract fixes the sign of a zero code, the NaN
 // block and the exponent clamp bit for bit, and those cases were never measured against the hardware conversions.
 // ---------------------------------------------------------------------------------------------------
-#define MX_PUT(ptr, v) do { if (WT) st_wt(ptr, v); else *(ptr) = (v); } while (0)
 #define MX_NAN ((u16)0x7e00)
 
 // The scale byte of the block whose largest magnitude (fp16 bits without the sign) is `a`: 0xFF for a block with a NaN or an inf, else
@@ -100,10 +100,10 @@ __device__ __forceinline__ void mx_compress_unit(const cfx_comp_item& it, size_t
     w |= (unsigned)__shfl_down((int)sbyte, 8, 64) << 16;
     w |= (unsigned)__shfl_down((int)sbyte, 12, 64) << 24;
     if (!live) return;
-    MX_PUT(&code[e / 8], codes);
+    st_put<WT>(&code[e / 8], codes);
     if ((threadIdx.x & 15) == 0) {
-        if (e + 128 <= E) MX_PUT((unsigned*)(scale + e / 32), w);
-        else MX_PUT((u16*)(scale + e / 32), (u16)w);
+        if (e + 128 <= E) st_put<WT>((unsigned*)(scale + e / 32), w);
+        else st_put<WT>((u16*)(scale + e / 32), (u16)w);
     }
     if (upd) {
         h16x8 out;
@@ -115,113 +115,34 @@ __device__ __forceinline__ void mx_compress_unit(const cfx_comp_item& it, size_t
     }
 }
 
-__global__ __launch_bounds__(256) void k_mx_compress(BatchC batch, size_t E, int flags) {
-    const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    const bool live = e < E;
-    const size_t ec = live ? e : 0;                       // (no lane leaves before the cross-lane steps: clamped loads, no stores)
-    const cfx_comp_item it = batch.it[blockIdx.y];
-    const h16x8 xv = ld8nt((const h16*)it.x + ec);
-    h16x8 bv = (h16x8)(h16)0;
-    if (it.base) bv = ld8nt((const h16*)it.base + ec);
-    mx_compress_unit<false>(it, e, E, live, flags, xv, bv);
-}
-
-// What a receiver needs for the 8 elements at flat offset e: one code word and the block's scale byte, from a packet read with plain
-// loads (MODE 0), with L2-bypassing loads (1: another workgroup of this launch wrote it) or with system-scope loads (2: another GPU did).
-// Load and use are apart so that a caller can put several units' loads in flight.
-struct MxRecv { unsigned codes; unsigned char sbyte; };
-template <int MODE>
-__device__ __forceinline__ void mx_recv_load(MxRecv& r, const unsigned* code, const unsigned char* scale, size_t e) {
-    r.codes = MODE == 0 ? code[e / 8] : (MODE == 1 ? ld_wt(code + e / 8) : ld_sys(code + e / 8));
-    r.sbyte = MODE == 0 ? scale[e / 32] : (MODE == 1 ? ld_wt(scale + e / 32) : ld_sys(scale + e / 32));
-}
-
-// ---- the MXFP4 layer in ONE launch (cfx_compress_batch_gated / the exchange-layer ops), k_topk_layer's structure: group S compresses the
-// own tensors and counts itself on the gate; group D - launched with it - holds the peers' state rows in registers until the gate (or the
-// external gate: the packets of the other ranks) opens, then reads code words + scale bytes and stores.
-#define MXL_SU 4                // units (8 elements a thread) of an S workgroup: 8192 elements, their loads in flight together
-#define MXL_DU 8                // ... of a D workgroup: 16384 elements, 128 bytes of state a thread held across the wait
-struct MxLayerArgs {
-    size_t E;
-    int n_sw, n_st;             // S workgroups per own tensor / in all
-    int n_dw;                   // D workgroups per reconstruction item
-    int flags;
-    unsigned* gate; unsigned gate_expect;
-    unsigned* xgate; unsigned xexpect;
-    unsigned* err;
-    long long timeout;
-    int remote;
-    P2PInline p2p;
+// The codec as cfx_local.h's skeleton sees it.  What a receiver needs for the 8 elements at flat offset e: one code word and the block's
+// scale byte, from a packet read with plain loads (MODE 0), with L2-bypassing loads (1: another workgroup of this launch wrote it) or with
+// system-scope loads (2: another GPU did).  Load and use are apart so that a caller can put several units' loads in flight.
+struct MxCodec {
+    using El = ElemF16;
+    static constexpr bool ALL_LANES = true;
+    static constexpr bool MAKE_FIRST = false;
+    static constexpr int IN_FLIGHT = LOCAL_DU;            // every unit's packet words in flight at once, then the stores
+    struct Recv { unsigned codes; unsigned char sbyte; };
+    template <bool WT>
+    static __device__ __forceinline__ void compress_unit(const cfx_comp_item& it, size_t e, size_t E, bool live, int flags, h16x8 xv, h16x8 bv) {
+        mx_compress_unit<WT>(it, e, E, live, flags, xv, bv);
+    }
+    template <int MODE>
+    static __device__ __forceinline__ void recv_load(Recv& r, const void* packet, size_t E, size_t e) {
+        const unsigned* code = (const unsigned*)packet;
+        const unsigned char* scale = (const unsigned char*)packet + E / 2;
+        r.codes = MODE == 0 ? code[e / 8] : (MODE == 1 ? ld_wt(code + e / 8) : ld_sys(code + e / 8));
+        r.sbyte = MODE == 0 ? scale[e / 32] : (MODE == 1 ? ld_wt(scale + e / 32) : ld_sys(scale + e / 32));
+    }
+    static __device__ __forceinline__ h16x8 recv_make(const Recv& r, size_t) { return mx_recv(r.codes, r.sbyte); }
 };
-__global__ __launch_bounds__(256) void k_mx_layer(BatchC batch, BatchD gated, MxLayerArgs a) {
-    int b = blockIdx.x;
-    if (b < a.n_st) {
-        const int z = b / a.n_sw, sw = b - z * a.n_sw;
-        const cfx_comp_item it = batch.it[z];
-        h16x8 xv[MXL_SU], xb[MXL_SU];
-#pragma unroll
-        for (int u = 0; u < MXL_SU; ++u) {                  // every unit's loads first (clamped offset: unconditional)
-            const size_t e = (((size_t)sw * MXL_SU + u) * 256 + threadIdx.x) * 8, ec = e < a.E ? e : 0;
-            xv[u] = ld8nt((const h16*)it.x + ec);
-            xb[u] = it.base ? ld8nt((const h16*)it.base + ec) : (h16x8)(h16)0;
-        }
-#pragma unroll
-        for (int u = 0; u < MXL_SU; ++u) {
-            const size_t e = (((size_t)sw * MXL_SU + u) * 256 + threadIdx.x) * 8;
-            mx_compress_unit<true>(it, e, a.E, e < a.E, a.flags, xv[u], xb[u]);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) gate_arrive(a.gate, 1u, a.gate_expect);
-        // (packets complete = the word the gate's last arriver writes for XCD 0)
-        if (b == 0 && a.p2p.own) p2p_exchange_inline(a.gate + GATE_LINE, a.gate_expect, 1, a.p2p, a.xgate, a.xexpect, a.err);
-        return;
-    }
-    b -= a.n_st;
-    const int item = b / a.n_dw, dw = b - item * a.n_dw;
-    const cfx_decomp_item it = gated.it[item];
-    const h16* base = (const h16*)it.base;
-    h16* out = (h16*)it.recon;
-    h16x8 bv[MXL_DU];
-#pragma unroll
-    for (int u = 0; u < MXL_DU; ++u) {
-        const size_t e = (((size_t)dw * MXL_DU + u) * 256 + threadIdx.x) * 8;
-        bv[u] = (base && e < a.E) ? ld8nt(base + e) : (h16x8)(h16)0;
-    }
-    if (!(a.xgate ? gate_wait<true>(a.xgate, a.xexpect, a.err, a.timeout) : gate_wait<false>(a.gate, a.gate_expect, a.err, a.timeout))) return;
-    const unsigned* code = (const unsigned*)it.packet;
-    const unsigned char* scale = (const unsigned char*)it.packet + a.E / 2;
-    MxRecv rr[MXL_DU];                                      // every unit's packet words in flight at once, then the stores
-#pragma unroll
-    for (int u = 0; u < MXL_DU; ++u) {
-        const size_t e = (((size_t)dw * MXL_DU + u) * 256 + threadIdx.x) * 8, ec = e < a.E ? e : 0;
-        if (a.remote) mx_recv_load<2>(rr[u], code, scale, ec);
-        else mx_recv_load<1>(rr[u], code, scale, ec);
-    }
-#pragma unroll
-    for (int u = 0; u < MXL_DU; ++u) {
-        const size_t e = (((size_t)dw * MXL_DU + u) * 256 + threadIdx.x) * 8;
-        if (e < a.E) {
-            const h16x8 rv = mx_recv(rr[u].codes, rr[u].sbyte);
-            st8nt(out + e, base ? (bv[u] + rv) : rv);
-        }
-    }
-}
 
+// stand-alone compress / decompress and the layer in ONE launch: cfx_local.h's bodies
+__global__ __launch_bounds__(256) void k_mx_compress(BatchC batch, size_t E, int flags) { local_compress<MxCodec>(batch, E, flags); }
+__global__ __launch_bounds__(256) void k_mx_layer(BatchC batch, BatchD gated, LocalLayerArgs a) { LOCAL_LAYER(batch, gated, a, MxCodec); }
 __global__ __launch_bounds__(256) void k_mx_decompress(BatchD batch, size_t E, unsigned* pre, unsigned pre_val) {
-    // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
-    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
-    const cfx_decomp_item it = batch.it[blockIdx.y];
-    const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    if (e >= E) return;                                      // (nothing travels between lanes here)
-    const h16* base = (const h16*)it.base;
-    h16* out = (h16*)it.recon;
-    MxRecv rr;
-    mx_recv_load<0>(rr, (const unsigned*)it.packet, (const unsigned char*)it.packet + E / 2, e);
-    h16x8 bv = (h16x8)(h16)0;
-    if (base) bv = ld8nt(base + e);
-    const h16x8 recv = mx_recv(rr.codes, rr.sbyte);
-    st8nt(out + e, base ? (bv + recv) : recv);
+    local_decompress<MxCodec>(batch, E, pre, pre_val);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -229,67 +150,20 @@ __global__ __launch_bounds__(256) void k_mx_decompress(BatchD batch, size_t E, u
 // ---------------------------------------------------------------------------------------------------
 int cfx_i_mx_compress(CompressCall& cc) {
     cfx_ctx* ctx = cc.ctx;
-    const int N = cc.N, C = cc.C, flags = cc.flags, batch = cc.batch, n_gated = cc.n_gated;
-    const cfx_comp_item* items = cc.items;
-    const cfx_decomp_item* gated = cc.gated;
-    void* stream = cc.stream;
-    hipStream_t s = (hipStream_t)stream;
-    CfxXGate* xg = cc.xg;
-    const size_t E = (size_t)N * C;
-    // ---- the layer in ONE launch (k_mx_layer): the reconstruction group launched with the compress group, gated on the packets ----
-    const int stream_cus = n_gated ? stream_cu_count(ctx, stream) : 0;
-    bool layer = n_gated && ctx->gated_on && !ctx->dev_probe && stream_cus >= 128 && !cc.capturing;
-    if (layer && !xg) {
-        // loop-back: every reconstruction item reads one of this launch's packets
-        for (int g_ = 0; g_ < n_gated && layer; ++g_) {
-            bool mine = false;
-            for (int i = 0; i < batch; ++i) mine = mine || gated[g_].packet == items[i].packet;
-            layer = mine;
-        }
-    }
-    if (layer && !ctx->tick && cfx_prepare(ctx) != CFX_OK) return CFX_ERR_LAUNCH;
-    if (layer) {
-        if (ctx->gate_err && *(volatile unsigned*)ctx->gate_err)
-            return fail(ctx, CFX_ERR_GATE, "compress: an earlier gate / flag wait on this context timed out (cfx_gate_errors reads and clears the count)");
-        const unsigned slot = ticket_slot(ctx, stream);
-        MxLayerArgs a;
-        memset(&a, 0, sizeof(a));
-        a.E = E;
-        a.n_sw = (int)((E / 8 + 256 * MXL_SU - 1) / (256 * MXL_SU));
-        a.n_st = a.n_sw * batch;
-        a.n_dw = (int)((E / 8 + 256 * MXL_DU - 1) / (256 * MXL_DU));
-        a.flags = flags;
-        a.gate = ctx->gate + (size_t)slot * GATE_STRIDE;
-        ctx->gate_expect[3 * slot] += (unsigned)a.n_st;
-        a.gate_expect = ctx->gate_expect[3 * slot];
-        a.err = ctx->gate_err;
-        a.timeout = ctx->gate_timeout;
-        if (xg) {
-            a.xgate = a.gate + GATE_BLOCK;
-            a.xexpect = ++ctx->gate_expect[3 * slot + 1];
-            a.remote = xg->remote;
-            fill_p2p(ctx, xg, a.p2p);
-            xg->taken = 1;
-            xg->p_gate = a.gate + GATE_LINE; xg->p_expect = a.gate_expect;      // the word the gate's last arriver writes for XCD 0
-            xg->f_gate = a.xgate; xg->f_expect = a.xexpect;
-        }
-        const dim3 g((unsigned)(a.n_st + a.n_dw * n_gated));
-        LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, k_mx_layer, g, dim3(256), 0, s, cc.b, cc.gd, a);
+    hipStream_t s = (hipStream_t)cc.stream;
+    LocalLayerArgs a;
+    const int lg = cfx_i_local_layer(cc, a);
+    if (lg < 0) return lg;
+    if (lg) {
+        LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, k_mx_layer, dim3((unsigned)lg), dim3(256), 0, s, cc.b, cc.gd, a);
         return check_launch(ctx, "mxfp4 layer launch");
     }
-    const dim3 g((unsigned)((E / 8 + 255) / 256), batch);
-    LAUNCH(ctx, KID_TOPK_COMPRESS, s, k_mx_compress, g, dim3(256), 0, s, cc.b, E, flags);
-    const int rc = check_launch(ctx, "mxfp4 compress launch");
-    // no layer form here: an exchange-layer op runs its exchange and the reconstruction behind this call; a plain gated call gets the
-    // reconstruction in stream order
-    if (rc != CFX_OK || xg || !n_gated) return rc;
-    return cfx_i_decompress_impl(ctx, cc.codec, N, C, cc.param, n_gated, gated, stream, nullptr, 0u);
+    LAUNCH(ctx, KID_TOPK_COMPRESS, s, k_mx_compress, cfx_i_local_grid(cc.N, cc.C, cc.batch), dim3(256), 0, s, cc.b, (size_t)cc.N * cc.C, cc.flags);
+    return cfx_i_local_tail(cc, "mxfp4 compress launch");
 }
 
 int cfx_i_mx_decompress(cfx_ctx* ctx, int N, int C, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val) {
     hipStream_t s = (hipStream_t)stream;
-    const size_t E = (size_t)N * C;
-    const dim3 g((unsigned)((E / 8 + 255) / 256), batch);
-    LAUNCH(ctx, KID_TOPK_DECOMPRESS, s, k_mx_decompress, g, dim3(256), 0, s, b, E, pre, pre_val);
+    LAUNCH(ctx, KID_TOPK_DECOMPRESS, s, k_mx_decompress, cfx_i_local_grid(N, C, batch), dim3(256), 0, s, b, (size_t)N * C, pre, pre_val);
     return check_launch(ctx, "decompress launch");
 }
