@@ -167,11 +167,12 @@ SYMBOLS = [
 ]
 
 # include/cfx_dev.h: exported by the DEVELOPER library only (libcfx_dev.so, -DCFX_DEV_PROBES).  Bound when - and only when - that library
-# was loaded in place of the product one (CFX_LIBCFX_PATH, or use_dev_library() before the first load): tools/*_stamps.py, tests/tagwrap_child.py
+# was loaded in place of the product one (CFX_LIBCFX_PATH, or use_dev_library() before the first load): tools/*_stamps.py, tests/tagwrap_child.py, tests/lr_q4_child.py
 DEV_SYMBOLS = [
     ("cfx_dev_stamps", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     ("cfx_dev_set_launch_tags", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint]),
     ("cfx_dev_set_probe", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("cfx_dev_lr_q4", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_void_p)] * 5 + [ctypes.c_void_p]),
 ]
 
 _lib = None

@@ -1090,4 +1090,28 @@ int cfx_lr_decompress_batch(cfx_ctx* ctx, int quantized, int N, int C, int rank,
     return cfx_i_lr_decode_launch(ctx, N, C, rank, batch, dec, true, s);
 }
 
+#ifdef CFX_DEV_PROBES      // ---- the developer library only (include/cfx_dev.h) ----
+// k_lr_q4 on the caller's fp16 factors, with the launch geometry cfx_lr_compress_batch gives it (the chains hand it the factors in their
+// workspace, where no test can put a matrix)
+int cfx_dev_lr_q4(cfx_ctx* ctx, int N, int C, int rank, int want_dq, int batch, const void* const* U, const void* const* Vt,
+                  void* const* packet, void* const* Uq, void* const* Vtq, void* stream) {
+    if (!ctx || !U || !Vt || !packet || (want_dq && (!Uq || !Vtq))) return fail(ctx, CFX_ERR_NULL, "dev lr q4: null ctx/arrays");
+    if (batch < 1 || batch > LR_MAXB) return fail(ctx, CFX_ERR_BATCH, "dev lr q4: batch out of range");
+    if (!lr_shape_ok(1, N, C, rank)) return fail(ctx, CFX_ERR_SHAPE, "dev lr q4: bad shape/rank");
+    const size_t secU = (size_t)N * rank / 2 + 4 * rank;
+    LrQ4Batch qb;
+    memset(&qb, 0, sizeof(qb));
+    for (int i = 0; i < batch; ++i) {
+        if (!U[i] || !Vt[i] || !packet[i] || (want_dq && (!Uq[i] || !Vtq[i]))) return fail(ctx, CFX_ERR_NULL, "dev lr q4: null factor/packet");
+        if (!AL16(U[i]) || !AL16(Vt[i]) || !AL16(packet[i]) || (want_dq && (!AL16(Uq[i]) || !AL16(Vtq[i]))))
+            return fail(ctx, CFX_ERR_ALIGN, "dev lr q4: pointers must be 16-byte aligned");
+        unsigned char* pk = (unsigned char*)packet[i];
+        qb.it[i] = {(const h16*)U[i], (const h16*)Vt[i], pk, pk + secU, Uq ? (h16*)Uq[i] : nullptr, Vtq ? (h16*)Vtq[i] : nullptr};      // (want_dq = 0: the kernel is handed them and leaves them alone)
+    }
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(ctx, KID_INT4_QUANT, s, k_lr_q4, dim3(lrq_u_shares(N) + LRQ_VS, batch), dim3(1024), 0, s, qb, N, C, rank, want_dq ? 1 : 0, lrq_u_shares(N));
+    return check_launch(ctx, "dev lr q4 launch");
+}
+#endif
+
 }  // extern "C"

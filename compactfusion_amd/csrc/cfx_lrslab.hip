@@ -24,7 +24,8 @@
 // Everything r x r sized - the fp64 Gram
 // matrices (v_mfma_f64_16x16x4_f64 over the fp32 values: exact products), the factorisations, Y = W T (v_mfma_f32_16x16x4_f32) - is
 // done by every workgroup redundantly: nobody waits for a broadcast.  V = U^T slab and the state update of the slab's columns come
-// from the registers the slab and base were loaded into at the start, with the arithmetic of k_lr_decode (the receiver's kernel).
+// from the registers the slab and base were loaded into at the start, with the arithmetic of k_lr_decode (the receiver's kernel) -
+// only where k_lr_decode IS the receiver's kernel: at rank 32 or after cfx_set_lr_decode(ctx, 2) the caller runs the MFMA form instead.
 //
 // The workgroups of a launch wait for each other: the host only takes this form when C / 32 workgroups per tensor are co-resident
 // on the CUs the stream may use (one workgroup per CU: ~150 KB of LDS); otherwise the multi-launch chains run.
@@ -883,6 +884,10 @@ int cfx_i_lrs_factors(cfx_ctx* ctx, int quantized, int N, int C, int rank, int b
     if (fit < 1) return fail(ctx, CFX_ERR_LAUNCH, "low-rank: the slab-resident chain does not fit the stream's CUs");
     const size_t npk = lrs_npk(N);
     (void)extra;
+    // The launch does the sender's update itself only where the receiver's kernel is the VALU form, whose v_dot2 order it reproduces: the
+    // automatic choice up to rank 16, not after cfx_set_lr_decode(ctx, 2).  Otherwise (rank 32, or the MFMA form forced) the caller runs
+    // the receiver's kernel - the MFMA form sums in another order, and sender and receiver have to agree bit for bit.
+    const int fuse = (want_decode && !quantized && RPv <= 16 && ctx->lr_decode != 2) ? 1 : 0;
     for (int first = 0; first < batch; first += fit) {
         const int nb = batch - first < fit ? batch - first : fit;
         LrBatch bb;
@@ -892,7 +897,7 @@ int cfx_i_lrs_factors(cfx_ctx* ctx, int quantized, int N, int C, int rank, int b
         memset(&a, 0, sizeof(a));
         a.N = N; a.C = C; a.NPK = (int)npk; a.r = rank; a.batch = nb; a.nwg_t = C / LRS_SW;
         a.absd = absd; a.u_in_packet = quantized ? 0 : 1;
-        a.fuse_decode = (want_decode && !quantized && RPv <= 16) ? 1 : 0;      // (rank 32: the receiver's kernel is the MFMA form - the caller runs it)
+        a.fuse_decode = fuse;
         a.offU16 = offU16; a.offV16 = offV16;
         a.arena = lrs_arena(ctx, (void*)s, N, C, RPv, nb, &a.arena_stride, &a.offFull);
         a.tick = cfx_i_ticket_block(ctx, (void*)s);
@@ -903,6 +908,6 @@ int cfx_i_lrs_factors(cfx_ctx* ctx, int quantized, int N, int C, int rank, int b
         const int rc = RPv == 8 ? lrs_run<8>(ctx, bb, a, s) : (RPv == 16 ? lrs_run<16>(ctx, bb, a, s) : lrs_run<32>(ctx, bb, a, s));
         if (rc != CFX_OK) return rc;
     }
-    if (decoded) *decoded = (want_decode && !quantized && RPv <= 16) ? 1 : 0;
+    if (decoded) *decoded = fuse;
     return CFX_OK;
 }

@@ -309,7 +309,8 @@ int cfx_set_fused_finalize(cfx_ctx* ctx, int on);
  *                         the one-launch forms where they qualify)
  *   cfx_set_lr_chain      low-rank factor chain: 0 = automatic (slab-resident single launch where its workgroups fit the stream, else
  *                         the six-launch N-space chain, else the C-space chain), 1 = never the single launch, 2 = C-space chain only
- *   cfx_set_lr_decode     low-rank reconstruction kernel: 0 = automatic (MFMA form at rank 32), 1 = VALU form, 2 = MFMA form */
+ *   cfx_set_lr_decode     low-rank reconstruction kernel: 0 = automatic (MFMA form at rank 32), 1 = VALU form, 2 = MFMA form.  The
+ *                         sender's error-feedback update follows the switch: its state stays the receiver's reconstruction bit for bit */
 int cfx_set_stats_rows(cfx_ctx* ctx, int rows);
 int cfx_set_gated_launch(cfx_ctx* ctx, int on);
 int cfx_set_lr_chain(cfx_ctx* ctx, int chain);

@@ -2,7 +2,7 @@
  * `python -m compactfusion_amd.build --dev-probes`).  NOT part of the product ABI: libcfx.so exports none of these symbols, its kernels carry
  * no probe argument and no probe branch (csrc/cfx_internal.h: `Probe` is an empty type there), and compactfusion_amd/_lib.py does not bind
  * them.  Users: tools/*_stamps.py, tools/fused_probe.py (timelines of the layer launches and of the slab-resident low-rank chain) and
- * tests/tagwrap_child.py (walks a context across the wrap of its launch tags). */
+ * tests/tagwrap_child.py (walks a context across the wrap of its launch tags), tests/lr_q4_child.py (the low-rank factor quantiser alone). */
 #ifndef CFX_DEV_H
 #define CFX_DEV_H
 #include "cfx.h"
@@ -24,6 +24,11 @@ int cfx_dev_set_launch_tags(cfx_ctx* ctx, unsigned abs_seq, unsigned mml_seq);
  * chooses; s = 0 gives the choice back.  For the sweep behind profiles/scale_jobs_split_sweep.md - the split is no product knob. */
 #define CFX_DEV_SCALE_SPLIT 0x100
 int cfx_dev_set_probe(cfx_ctx* ctx, int mode);
+/* k_lr_q4 alone on given fp16 factors: U (N, r), Vt (C, r) -> the two packet sections and, want_dq, the dequantised factors
+ * (LOW_RANK_Q shapes: N, C even, rank % 8 == 0; every pointer 16-byte aligned; the launch geometry of cfx_lr_compress_batch).  The chains
+ * hand the quantiser their factors in the workspace; this is how tests/lr_q4_child.py hands it a matrix. */
+int cfx_dev_lr_q4(cfx_ctx* ctx, int N, int C, int rank, int want_dq, int batch, const void* const* U, const void* const* Vt,
+                  void* const* packet, void* const* Uq, void* const* Vtq, void* stream);
 
 #ifdef __cplusplus
 }

@@ -191,7 +191,7 @@ def test_product_library_has_no_developer_entry_points():
     lib = _lib.load()
     hdr = open(os.path.join(REPO, "include", "cfx_dev.h")).read()
     dev_syms = re.findall(r"^int\s+(cfx_dev_\w+)\s*\(", hdr, flags=re.M)
-    assert sorted(dev_syms) == sorted(n for n, _, _ in _lib.DEV_SYMBOLS) and len(dev_syms) == 3
+    assert sorted(dev_syms) == sorted(n for n, _, _ in _lib.DEV_SYMBOLS) and len(dev_syms) == 4
     exported = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
     assert not re.search(r"debug|cfx_dev_|stamp", exported), "the product library exports a developer symbol"
     for sym in dev_syms:
@@ -204,3 +204,24 @@ def test_product_library_has_no_developer_entry_points():
     # no kernel of the product build mentions a probe: the only `Probe` with a pointer in it sits behind the macro
     src = open(os.path.join(REPO, "compactfusion_amd", "csrc", "cfx_internal.h")).read()
     assert "#ifdef CFX_DEV_PROBES\nstruct Probe {\n    unsigned long long* p;" in src
+    # cfx_dev_lr_q4 (the low-rank factor quantiser alone) sits behind the macro too, and checks its arguments before any HIP call
+    lrsrc = open(os.path.join(REPO, "compactfusion_amd", "csrc", "cfx_lowrank.hip")).read()
+    assert lrsrc.index("#ifdef CFX_DEV_PROBES") < lrsrc.index("int cfx_dev_lr_q4(") < lrsrc.rindex("#endif")
+    import ctypes
+    dl = ctypes.CDLL(dev)
+    for name, res, args in _lib.DEV_SYMBOLS:
+        getattr(dl, name).restype, getattr(dl, name).argtypes = res, args
+    dl.cfx_create.restype, dl.cfx_create.argtypes = ctypes.c_void_p, [ctypes.c_int]
+    dl.cfx_destroy.restype, dl.cfx_destroy.argtypes = None, [ctypes.c_void_p]
+    ctx = dl.cfx_create(0)
+    assert ctx
+    P = ctypes.c_void_p * 1
+    u, vt, pk, uq, vq = P(0x1000), P(0x2000), P(0x3000), P(0x4000), P(0x5000)
+    assert dl.cfx_dev_lr_q4(ctx, 2, 8, 8, 1, 1, u, vt, pk, None, None, None) == -1          # want_dq without Uq / Vtq
+    assert dl.cfx_dev_lr_q4(ctx, 2, 8, 8, 0, 1, u, None, pk, uq, vq, None) == -1
+    assert dl.cfx_dev_lr_q4(ctx, 2, 8, 8, 1, 0, u, vt, pk, uq, vq, None) == -5 and dl.cfx_dev_lr_q4(ctx, 2, 8, 8, 1, 17, u, vt, pk, uq, vq, None) == -5
+    assert dl.cfx_dev_lr_q4(ctx, 3, 8, 8, 1, 1, u, vt, pk, uq, vq, None) == -2               # LOW_RANK_Q: N even
+    assert dl.cfx_dev_lr_q4(ctx, 2, 8, 12, 1, 1, u, vt, pk, uq, vq, None) == -2              # ... rank % 8
+    assert dl.cfx_dev_lr_q4(ctx, 2, 8, 8, 1, 1, u, vt, P(0x3008), uq, vq, None) == -3        # misaligned packet
+    assert dl.cfx_dev_lr_q4(ctx, 2, 8, 8, 1, 1, u, vt, P(None), uq, vq, None) == -1
+    dl.cfx_destroy(ctx)
