@@ -24,6 +24,7 @@ class Codec(IntEnum):
     INT2_MINMAX = 6   # residual 4-level per-channel min/max (compress_quantize.py:386-426 on delta), four rows per byte
     MXFP4 = 8    # residual FP4 E2M1 elements with one E8M0 scale per 32 of a row (OCP Microscaling; include/cfx.h "MXFP4"); 7 is no codec
     BINARY_BLOCK = 10   # residual sign bits with one fp16 abs-mean per param = 32 / 64 / 128 of a row (include/cfx.h "BINARY_BLOCK"); 9 is no codec
+    INT2_BLOCK = 12     # residual 2-bit sign / magnitude codes with one fp16 abs-mean per param = 32 / 64 / 128 of a row (include/cfx.h "INT2_BLOCK"); 11 is no codec
 
 
 _ctx = {}

@@ -196,6 +196,31 @@ def sim_binary_block(input_tensor: torch.Tensor, block: int = 64):
     return dequantize_binary_block(*quantize_binary_block(input_tensor, block))
 
 
+# ---- INT2_BLOCK (extension: not in the reference; include/cfx.h "INT2_BLOCK") ---------------------------------------
+def quantize_int2_block(input_tensor: torch.Tensor, block: int = 64):
+    """-> codes (N, C/4) uint8 [INT2's layout: bits 2i, 2i+1 of byte [n][j] = (x[n][4j+i] >= 0) << 1 | (|x[n][4j+i]| > scale)], scales
+    (N, C/block) fp16 [the abs-mean of each block of `block` consecutive elements of a row].  The native INT2_BLOCK wire codec at residual 0."""
+    x = _nc(input_tensor)
+    N, C = x.shape
+    assert block in (32, 64, 128), f"block size must be 32, 64 or 128, got {block}"
+    assert C % max(block, 64) == 0, f"Dimension C (1) size must be a multiple of {max(block, 64)} for blocks of {block}, got {C}"
+    pkt, _ = codecs.compress(K.INT2_BLOCK, x, None, N, C, block, update_cache=False)
+    return pkt[:N * C // 8].view(torch.uint8).view(N, C // 4), pkt[N * C // 8:].view(N, C // block)
+
+
+def dequantize_int2_block(codes: torch.Tensor, scales: torch.Tensor):
+    assert codes.dtype == torch.uint8 and scales.dtype == torch.half
+    N, C4 = codes.shape
+    C = C4 * 4
+    block = C // scales.shape[1]
+    assert scales.shape[0] == N and block in (32, 64, 128) and scales.shape[1] * block == C
+    return codecs.decompress(K.INT2_BLOCK, _cat_packet(codes, scales), None, N, C, block)
+
+
+def sim_int2_block(input_tensor: torch.Tensor, block: int = 64):
+    return dequantize_int2_block(*quantize_int2_block(input_tensor, block))
+
+
 def sim_int4(input_tensor: torch.Tensor, dim):
     x = _nc(input_tensor)
     if dim == 1:

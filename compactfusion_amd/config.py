@@ -33,6 +33,8 @@ lowrank_lane           CFX_LOWRANK_LANE              on | off - on: a LOW_RANK /
                                                      beside the attention blocks; off: the whole layer op on the caller's stream
 binary_block           CFX_BINARY_BLOCK              32 | 64 | 128 - block size of COMPACT_COMPRESS_TYPE.BINARY_BLOCK (native codec 10): elements of a row
                                                      that share one fp16 scale (64); read when a layer is (re)built
+int2_block             CFX_INT2_BLOCK                32 | 64 | 128 - block size of COMPACT_COMPRESS_TYPE.INT2_BLOCK (native codec 12): elements of a row
+                                                     that share one fp16 scale (64); read when a layer is (re)built
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process
 """
@@ -53,6 +55,7 @@ _SETTINGS = {
     "lane_exchange_cus": ("CFX_LANE_EXCHANGE_CUS", "32", None),
     "lowrank_lane": ("CFX_LOWRANK_LANE", "on", ("on", "off")),
     "binary_block": ("CFX_BINARY_BLOCK", "64", ("32", "64", "128")),
+    "int2_block": ("CFX_INT2_BLOCK", "64", ("32", "64", "128")),
 }
 _explicit: Dict[str, str] = {}
 

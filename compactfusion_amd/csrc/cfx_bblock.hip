@@ -14,6 +14,7 @@
 #include "cfx_device.h"
 #include "cfx_host.h"
 #include "cfx_local.h"
+#include "cfx_bscale.h"
 
 // ---------------------------------------------------------------------------------------------------
 // One lane owns 8 consecutive flat elements (one 16-byte load of x, one of base, one byte of sign bits); a block is B / 8 = 4, 8 or 16
@@ -21,26 +22,6 @@
 // of lanes).  The block's scale is the exact integer sum of |d| in units of 2^-24 (habs_units), rounded once to fp32 and once to fp16
 // (mean16): order-independent, so the lanes may add in any order.
 // ---------------------------------------------------------------------------------------------------
-
-// The sum of a u64 over the B / 8 lanes of a block, in every lane of the block.  A lane's 8 elements are below 2^43 units: the low 24
-// bits and the bits above travel as two 32-bit DPP sums (16 lanes: below 2^28 and 2^23), with no carry between them until the end.
-template <int B>
-__device__ __forceinline__ u64 bb_block_sum(u64 v) {
-    unsigned lo = (unsigned)v & 0xFFFFFFu, hi = (unsigned)(v >> 24);
-    lo += __builtin_amdgcn_update_dpp(0u, lo, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
-    hi += __builtin_amdgcn_update_dpp(0u, hi, 0xB1, 0xf, 0xf, true);
-    lo += __builtin_amdgcn_update_dpp(0u, lo, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
-    hi += __builtin_amdgcn_update_dpp(0u, hi, 0x4E, 0xf, 0xf, true);
-    if constexpr (B >= 64) {
-        lo += __builtin_amdgcn_update_dpp(0u, lo, 0x141, 0xf, 0xf, true);    // row_half_mirror: the other quad of the 8 lanes
-        hi += __builtin_amdgcn_update_dpp(0u, hi, 0x141, 0xf, 0xf, true);
-    }
-    if constexpr (B >= 128) {
-        lo += __builtin_amdgcn_update_dpp(0u, lo, 0x140, 0xf, 0xf, true);    // row_mirror: the other half of the 16 lanes
-        hi += __builtin_amdgcn_update_dpp(0u, hi, 0x140, 0xf, 0xf, true);
-    }
-    return ((u64)hi << 24) + lo;
-}
 
 // 8 sign bits (bit i: element i >= 0) + the block's scale (fp16 bits, never negative) -> what a receiver adds: +s or -s
 __device__ __forceinline__ h16x8 bb_recv(unsigned bits, unsigned sbits) {
@@ -125,20 +106,6 @@ __global__ __launch_bounds__(256) void k_bb_decompress(BatchD batch, size_t E, u
 // ---------------------------------------------------------------------------------------------------
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
-// one of the six instantiations of a kernel template: the element type x the block size (validated: 32, 64 or 128)
-#define BB_LAUNCH(bf16, B, kid, kern, grid, ...) \
-    do { \
-        if (bf16) { \
-            if ((B) == 32) LAUNCH(ctx, kid, s, (kern<ElemBF16, 32>), grid, dim3(256), 0, s, __VA_ARGS__); \
-            else if ((B) == 64) LAUNCH(ctx, kid, s, (kern<ElemBF16, 64>), grid, dim3(256), 0, s, __VA_ARGS__); \
-            else LAUNCH(ctx, kid, s, (kern<ElemBF16, 128>), grid, dim3(256), 0, s, __VA_ARGS__); \
-        } else { \
-            if ((B) == 32) LAUNCH(ctx, kid, s, (kern<ElemF16, 32>), grid, dim3(256), 0, s, __VA_ARGS__); \
-            else if ((B) == 64) LAUNCH(ctx, kid, s, (kern<ElemF16, 64>), grid, dim3(256), 0, s, __VA_ARGS__); \
-            else LAUNCH(ctx, kid, s, (kern<ElemF16, 128>), grid, dim3(256), 0, s, __VA_ARGS__); \
-        } \
-    } while (0)
-
 int cfx_i_bb_compress(CompressCall& cc) {
     cfx_ctx* ctx = cc.ctx;
     hipStream_t s = (hipStream_t)cc.stream;
