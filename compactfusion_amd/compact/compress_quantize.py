@@ -221,6 +221,34 @@ def sim_int2_block(input_tensor: torch.Tensor, block: int = 64):
     return dequantize_int2_block(*quantize_int2_block(input_tensor, block))
 
 
+# ---- INT3_BLOCK (extension: not in the reference; include/cfx.h "INT3_BLOCK") ---------------------------------------
+def quantize_int3_block(input_tensor: torch.Tensor, block: int = 64):
+    """-> hi (N, C/4) uint8 [INT2's layout: bits 2i, 2i+1 of byte [n][j] = (x[n][4j+i] >= 0) << 1 | mag >> 1], lo (N, C/8) uint8 [BINARY's
+    layout: bit i of byte [n][j] = mag & 1 of x[n][8j+i]], scales (N, C/block) fp16 [the abs-mean of each block of `block` consecutive
+    elements of a row]; mag = 0..3 counts the thresholds 0.75 / 1.5 / 2.625 x scale that |x| exceeds.  The native INT3_BLOCK wire codec
+    at residual 0."""
+    x = _nc(input_tensor)
+    N, C = x.shape
+    assert block in (32, 64, 128), f"block size must be 32, 64 or 128, got {block}"
+    assert C % max(block, 64) == 0, f"Dimension C (1) size must be a multiple of {max(block, 64)} for blocks of {block}, got {C}"
+    pkt, _ = codecs.compress(K.INT3_BLOCK, x, None, N, C, block, update_cache=False)
+    raw = pkt.view(torch.uint8)
+    return raw[:N * C // 4].view(N, C // 4), raw[N * C // 4:3 * N * C // 8].view(N, C // 8), pkt[3 * N * C // 16:].view(N, C // block)
+
+
+def dequantize_int3_block(hi: torch.Tensor, lo: torch.Tensor, scales: torch.Tensor):
+    assert hi.dtype == torch.uint8 and lo.dtype == torch.uint8 and scales.dtype == torch.half
+    N, C4 = hi.shape
+    C = C4 * 4
+    block = C // scales.shape[1]
+    assert lo.shape == (N, C // 8) and scales.shape[0] == N and block in (32, 64, 128) and scales.shape[1] * block == C
+    return codecs.decompress(K.INT3_BLOCK, _cat_packet(hi, lo, scales), None, N, C, block)
+
+
+def sim_int3_block(input_tensor: torch.Tensor, block: int = 64):
+    return dequantize_int3_block(*quantize_int3_block(input_tensor, block))
+
+
 def sim_int4(input_tensor: torch.Tensor, dim):
     x = _nc(input_tensor)
     if dim == 1:

@@ -28,6 +28,10 @@ _CODECS = {
     "int2block32": (T.INT2_BLOCK, -1, False),
     "int2block64": (T.INT2_BLOCK, -1, False),
     "int2block128": (T.INT2_BLOCK, -1, False),
+    # extension: the block-scaled 3-bit codec; the preset sets configure(int3_block=B)
+    "int3block32": (T.INT3_BLOCK, -1, False),
+    "int3block64": (T.INT3_BLOCK, -1, False),
+    "int3block128": (T.INT3_BLOCK, -1, False),
 }
 # method -> PatchConfig arguments (use_compact, async_comm, async_warmup = the warm-up steps unless given)     configs.py:110-165
 _PATCH = {"int2patch": (True, False, None), "df": (False, True, None), "patch": (False, False, 0)}
@@ -59,6 +63,9 @@ def get_config(model_name: str, method: str) -> CompactConfig:
         if codec == T.INT2_BLOCK:
             from .. import config
             config.configure(int2_block=int(method[len("int2block"):]))
+        if codec == T.INT3_BLOCK:
+            from .. import config
+            config.configure(int3_block=int(method[len("int3block"):]))
         return CompactConfig(enabled=True, compress_func=_schedule(codec, warmup), comp_rank=rank, residual=1, ef=True, simulate=False,
                              log_stats=False, fastpath=fast)
     if method in _PATCH:

@@ -5,7 +5,7 @@ BINARY `[codes | U(N,1) | V(1,C)]` and SPARSE `[val | idx]` are single native la
 `lowrank.py`.  INT2 / INT4 / INT8 / IDENTITY are not slowpath wire codecs in the reference (ValueError, :80-81);
 here INT2 / INT4 / INT8 are accepted as an extension because BASELINE.json's configs use them as residual codecs, and
 INT2_MINMAX (simulation-only in the reference) as the native 4-level wire codec; MXFP4 (not in the reference) is the native block-scaled codec 8.
-BINARY_BLOCK (native codec 10) and INT2_BLOCK (native codec 12) are no slowpath wire codecs: their block size is a host switch, not an
+BINARY_BLOCK (native codec 10), INT2_BLOCK (native codec 12) and INT3_BLOCK (native codec 14) are no slowpath wire codecs: their block size is a host switch, not an
 argument of these functions (ValueError)."""
 from __future__ import annotations
 

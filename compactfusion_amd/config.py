@@ -35,6 +35,8 @@ binary_block           CFX_BINARY_BLOCK              32 | 64 | 128 - block size 
                                                      that share one fp16 scale (64); read when a layer is (re)built
 int2_block             CFX_INT2_BLOCK                32 | 64 | 128 - block size of COMPACT_COMPRESS_TYPE.INT2_BLOCK (native codec 12): elements of a row
                                                      that share one fp16 scale (64); read when a layer is (re)built
+int3_block             CFX_INT3_BLOCK                32 | 64 | 128 - block size of COMPACT_COMPRESS_TYPE.INT3_BLOCK (native codec 14): elements of a row
+                                                     that share one fp16 scale (64); read when a layer is (re)built
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process
 """
@@ -56,6 +58,7 @@ _SETTINGS = {
     "lowrank_lane": ("CFX_LOWRANK_LANE", "on", ("on", "off")),
     "binary_block": ("CFX_BINARY_BLOCK", "64", ("32", "64", "128")),
     "int2_block": ("CFX_INT2_BLOCK", "64", ("32", "64", "128")),
+    "int3_block": ("CFX_INT3_BLOCK", "64", ("32", "64", "128")),
 }
 _explicit: Dict[str, str] = {}
 

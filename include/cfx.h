@@ -41,6 +41,8 @@
  *           (no wire in the reference: the block-wise sign compressor of 1-bit Adam / block signSGD, B = param consecutive elements of a row)
  *   INT2_BLOCK [ codes N*C/4 B : INT2's code layout, element j of a row at bits 2(j%4) of byte j/4 | scale N*C/B fp16 : row-major, one per block ]
  *           (no wire in the reference: INT2's sign / magnitude levels around BINARY_BLOCK's block scale)
+ *   INT3_BLOCK [ hi N*C/4 B : 2-bit (sign<<1 | mag>>1), INT2's code layout | lo N*C/8 B : bit = mag & 1, BINARY's bit layout | scale N*C/B fp16 : row-major, one per block ]
+ *           (no wire in the reference: a sign and four magnitude levels around BINARY_BLOCK's block scale)
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
  *   and N odd, int4 with C % 16 == 8 and N/2 odd, INT2_MINMAX with C % 16 == 8 and N/4 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
  *   INT4 `min` of a channel whose minimum is zero: where zeros of BOTH signs occur among the channel's deltas, `min` may hold either zero
@@ -125,7 +127,33 @@
  *   cfx_plan_set_second_order (CFX_ERR_CODEC: residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items
  *   (CFX_ERR_CODEC), any other high bit on the codec argument (CFX_ERR_CODEC, sizes 0).  Id 11 is no codec.
  *
- * bf16 activations (CFX_CODEC_BINARY, CFX_CODEC_INT2, CFX_CODEC_BINARY_BLOCK and CFX_CODEC_INT2_BLOCK only)
+ * INT3_BLOCK (CFX_CODEC_INT3_BLOCK = 14, param = the block size B in {32, 64, 128}; any other param: CFX_ERR_SHAPE, sizes 0): a sign and
+ *   one of four magnitude levels, thresholds and levels taken from BINARY_BLOCK's scale - the abs-mean of the block of B consecutive
+ *   elements of a row the element lies in.  Nothing global to wait for, as for BINARY_BLOCK.  Bit for bit, one rounding per line:
+ *       d        = fp16(x - base)                                 (base NULL: x)
+ *       s        = fp16( fp32(exact sum of |d| over the block, in units of 2^-24) / fp32(B) )         (BINARY_BLOCK's scale)
+ *       t_k      = fp16( min( fp32(s) * T_k, 65504 ) )            T = {0.75, 1.5, 2.625}   (products exact in fp32; round to nearest even
+ *                                                                 to fp16, subnormals included)
+ *       l_k      = fp16( min( fp32(s) * L_k, 65504 ) )            L = {0.375, 1.125, 1.875, 3.375}   (saturating: never inf into a state)
+ *       sign     = d >= 0                                         (-0 gives 1, as INT2_BLOCK)
+ *       mag      = (|d| > t_0) + (|d| > t_1) + (|d| > t_2)        (strict; compared as fp16 values = their magnitude bits as integers; 0..3)
+ *       recv     = (sign ? + : -) l_mag                           (s == 0: +0 / -0 by the sign bit)
+ *       new_base = recon = fp16(base + recv)                      (base NULL: recv, bits verbatim;  CFX_FLAG_NO_EF: new_base = x)
+ *   T and L: between the Lloyd-Max grids of a Gaussian and a Laplacian source of unit abs-mean, in eighths.  A scale past 65504 / 3.375
+ *   saturates l_3; past 65504 / 2.625 and 65504 / 1.5 a threshold is 65504 and mag 3, then 2, is unreachable.  s = 2^-24 gives t = 1, 2, 3
+ *   units and l_0 = 0.  Wire: three sections, no padding -
+ *       hi    N*C/4 bytes   2-bit (sign << 1 | mag >> 1), INT2's code layout: element j of a row at bits 2(j%4) of byte j/4
+ *       lo    N*C/8 bytes   bit = mag & 1, BINARY's bit layout: bit i of byte j of row n = element 8j+i
+ *       scale 2*N*C/B bytes fp16, row-major, one per block
+ *   Shapes are BINARY_BLOCK's: C % max(B, 64) == 0, any N >= 1; cfx_packet_bytes = 3*N*C/8 + 2*N*C/B (3.5 / 3.25 / 3.125 bits per
+ *   element); cfx_workspace_bytes is 0: callers pass NULL / 0.  CFX_ELEM_BF16 is accepted (codec argument 0x10E) under the "bf16
+ *   activations" rules below.  Forms and fall-backs are INT2_BLOCK's: stand-alone compress / decompress (kernel ids 13 and 14) and the
+ *   one-launch layer k_i3b_layer (id 31) under k_i2b_layer's conditions; otherwise, and under stream capture, compress ; (exchange) ;
+ *   decompress in stream order with the same results.  Refused, as for INT2_BLOCK: the second-order entry points and
+ *   cfx_plan_set_second_order (CFX_ERR_CODEC: residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items
+ *   (CFX_ERR_CODEC), any other high bit on the codec argument (CFX_ERR_CODEC, sizes 0).  Ids 13 and 15 are no codecs.
+ *
+ * bf16 activations (CFX_CODEC_BINARY, CFX_CODEC_INT2, CFX_CODEC_BINARY_BLOCK, CFX_CODEC_INT2_BLOCK and CFX_CODEC_INT3_BLOCK only)
  *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,
  *   cfx_compress[_batch[_ex|_gated]], cfx_decompress[_batch], cfx_plan_add_compress[_ex|_gated], cfx_plan_add_decompress,
  *   cfx_plan_add_exchange_layer[_p2p], and through them cfx_plan_copy_op) says that ALL tensor operands of the call - x, base, new_base,
@@ -133,7 +161,7 @@
  *   CFX_FLAG_ELEM_BF16 in `flags`.  The residual domain and the wire stay fp16:
  *       d        = fp16_rne( fp32(x) - fp32(base) )          one fp32 subtraction, one rounding to fp16; base NULL: d = fp16_rne(fp32(x))
  *       d -> recv  exactly the fp16 path: sign bits / 2-bit codes, exact sums in units of 2^-24, fp16 scales, packet bytes;
- *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels  or +-s of the block (BINARY_BLOCK)  or the block's two levels (INT2_BLOCK), in fp16
+ *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels  or +-s of the block (BINARY_BLOCK)  or the block's two / four levels (INT2_BLOCK / INT3_BLOCK), in fp16
  *       new_base = recon = bf16_rne( fp32(base) + fp32(recv) )     base NULL: bf16_rne(fp32(recv))
  *       CFX_FLAG_NO_EF: new_base = x, copied verbatim as bf16 bits
  *   Packet layout, cfx_packet_bytes and cfx_workspace_bytes are those of the fp16 codec: a bf16 sender's packet is a valid fp16-path
@@ -159,7 +187,7 @@
  *   In place is allowed: new_base == base, new_delta_base == delta_base.  base and delta_base are required (CFX_ERR_NULL); a
  *   reconstruction item may have new_delta_base NULL (update_cache = False: recon only); a compress item needs new_base and
  *   new_delta_base with CFX_FLAG_UPDATE_CACHE and writes only the packet without it.  CFX_ERR_CODEC before any launch: CFX_FLAG_NO_EF
- *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6, 8, 10 and 12 (those compose cfx_residual2_delta / _update
+ *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6, 8, 10, 12 and 14 (those compose cfx_residual2_delta / _update
  *   around the codec).  The second-order launches report the kernel ids of their first-order twins (cfx_profile_enable).
  *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
@@ -167,7 +195,7 @@
  *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
  *   TOPK:        |delta| is ranked as the reference's tl.argmax ranks it: NaN above everything, +inf included; the first NaN wins.
  *   MXFP4:       a block with a NaN or an inf delta is the 0xFF block above (codes 0, NaN reconstruction); its neighbours are untouched.
- *   BINARY / INT2 / BINARY_BLOCK / INT2_BLOCK: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
+ *   BINARY / INT2 / BINARY_BLOCK / INT2_BLOCK / INT3_BLOCK: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
  *                NaN; the outputs are finite garbage or NaN, and need not match the reference.
  */
 #ifndef CFX_H
@@ -208,9 +236,10 @@ enum cfx_codec {
     CFX_CODEC_INT2_MINMAX = 6, /* COMPACT_COMPRESS_TYPE.INT2_MINMAX: per-channel min/max 4 levels, four rows per byte; param 0 */
     CFX_CODEC_MXFP4 = 8,     /* COMPACT_COMPRESS_TYPE.MXFP4: FP4 E2M1 elements, one E8M0 scale per 32 of a row; param 0 (7 is no codec) */
     CFX_CODEC_BINARY_BLOCK = 10, /* COMPACT_COMPRESS_TYPE.BINARY_BLOCK: sign bits, one fp16 abs-mean per param = 32 / 64 / 128 of a row (9 is no codec) */
-    CFX_CODEC_INT2_BLOCK = 12 /* COMPACT_COMPRESS_TYPE.INT2_BLOCK: INT2's codes, one fp16 abs-mean per param = 32 / 64 / 128 of a row (11 is no codec) */
+    CFX_CODEC_INT2_BLOCK = 12, /* COMPACT_COMPRESS_TYPE.INT2_BLOCK: INT2's codes, one fp16 abs-mean per param = 32 / 64 / 128 of a row (11 is no codec) */
+    CFX_CODEC_INT3_BLOCK = 14 /* COMPACT_COMPRESS_TYPE.INT3_BLOCK: sign + 2 magnitude bits, one fp16 abs-mean per param = 32 / 64 / 128 of a row (13 is no codec) */
 };
-/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit, 2-bit and block-scaled 1-bit / 2-bit codecs; "bf16 activations" above) */
+/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs; "bf16 activations" above) */
 #define CFX_ELEM_BF16 0x100
 
 enum cfx_flags {

@@ -62,6 +62,13 @@ CONFIGS = [
     ("10e FLUX.1 1024^2 ring 8, INT2_BLOCK B=64 bf16 (config 3's shard)", 0x10C, 64, (544, 3072), 57, 2, 14, True),
     ("10f FLUX.1 1024^2 ring 8, INT2_BLOCK B=128 bf16 (config 3's shard)", 0x10C, 128, (544, 3072), 57, 2, 14, True),
     ("10g FLUX.1 1024^2 ring 8, INT2 bf16 (config 3's shard)", 0x102, 0, (544, 3072), 57, 2, 14, True),
+    # the block-scaled 3-bit codec (codec 14, param = the block size; 0x10E: bf16): four levels a sign between INT2_BLOCK and MXFP4
+    ("11a FLUX.1 1024^2 ring 8, INT3_BLOCK B=32 (config 3's shard)", 14, 32, (544, 3072), 57, 2, 14, True),
+    ("11b FLUX.1 1024^2 ring 8, INT3_BLOCK B=64 (config 3's shard)", 14, 64, (544, 3072), 57, 2, 14, True),
+    ("11c FLUX.1 1024^2 ring 8, INT3_BLOCK B=128 (config 3's shard)", 14, 128, (544, 3072), 57, 2, 14, True),
+    ("11d FLUX.1 1024^2 ring 8, INT3_BLOCK B=32 bf16 (config 3's shard)", 0x10E, 32, (544, 3072), 57, 2, 14, True),
+    ("11e FLUX.1 1024^2 ring 8, INT3_BLOCK B=64 bf16 (config 3's shard)", 0x10E, 64, (544, 3072), 57, 2, 14, True),
+    ("11f FLUX.1 1024^2 ring 8, INT3_BLOCK B=128 bf16 (config 3's shard)", 0x10E, 128, (544, 3072), 57, 2, 14, True),
 ]
 NAMES = {1: "binary", 2: "int2", 3: "int4", 4: "int8", 5: "topk"}
 # algorithmic bytes per element (compress + error feedback, reconstruct); low-rank: x + state in, state out (6), state in / out (4)
@@ -69,11 +76,11 @@ ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 +
 
 
 def alg_pair(cid, param=0):
-    """(compress + error feedback, reconstruct) bytes per element of a codec argument; the block-scaled 1-bit / 2-bit codecs: 1/8 resp.
-    1/4 + 2/B of packet"""
+    """(compress + error feedback, reconstruct) bytes per element of a codec argument; the block-scaled 1-bit / 2-bit / 3-bit codecs: 1/8,
+    1/4 resp. 3/8 + 2/B of packet"""
     cid &= 0xff
-    if cid in (10, 12):
-        pkt = (0.125 if cid == 10 else 0.25) + 2.0 / param
+    if cid in (10, 12, 14):
+        pkt = {10: 0.125, 12: 0.25, 14: 0.375}[cid] + 2.0 / param
         return 6 + pkt, 4 + pkt
     return ALG[cid]
 
@@ -208,7 +215,7 @@ def gpu_step(cid, param, N, C, L, ncomp, nrec, update, min_steps=20, budget_s=0.
 
 
 def cpu_step(cid, param, N, C, L, ncomp, nrec, update, budget=8.0):
-    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4, BINARY_BLOCK, INT2_BLOCK, bf16
+    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4, BINARY_BLOCK, INT2_BLOCK, INT3_BLOCK, bf16
         return None, 0
     from oracle import c_oracle as CO
     name = NAMES[cid]
