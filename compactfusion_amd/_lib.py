@@ -19,7 +19,7 @@ ERR_NAMES = {
 FLAG_UPDATE_CACHE = 1
 FLAG_NO_EF = 2
 FLAG_ELEM_BF16 = 0x100   # cfx_int2_quantize only
-ELEM_BF16 = 0x100        # CFX_ELEM_BF16: or-ed into a `codec` argument - the call's tensors are bf16 (1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit codecs)
+ELEM_BF16 = 0x100        # CFX_ELEM_BF16: or-ed into a `codec` argument - the call's tensors are bf16 (1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit codecs, MXINT8)
 MERGE_BSHD = 1           # cfx_attn_merge_ex `flags` (with ELEM_BF16: block_out / final_out are bf16)
 MERGE_FIRST = 2
 

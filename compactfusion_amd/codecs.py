@@ -26,6 +26,7 @@ class Codec(IntEnum):
     BINARY_BLOCK = 10   # residual sign bits with one fp16 abs-mean per param = 32 / 64 / 128 of a row (include/cfx.h "BINARY_BLOCK"); 9 is no codec
     INT2_BLOCK = 12     # residual 2-bit sign / magnitude codes with one fp16 abs-mean per param = 32 / 64 / 128 of a row (include/cfx.h "INT2_BLOCK"); 11 is no codec
     INT3_BLOCK = 14     # residual sign + 2 magnitude bits (four levels) with one fp16 abs-mean per param = 32 / 64 / 128 of a row (include/cfx.h "INT3_BLOCK"); 13 is no codec
+    MXINT8 = 16         # residual int8 elements (implied 2^-6) with one E8M0 scale per 32 of a row (OCP Microscaling; include/cfx.h "MXINT8"); 15 is no codec
 
 
 _ctx = {}

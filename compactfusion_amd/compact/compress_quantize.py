@@ -249,6 +249,29 @@ def sim_int3_block(input_tensor: torch.Tensor, block: int = 64):
     return dequantize_int3_block(*quantize_int3_block(input_tensor, block))
 
 
+# ---- MXINT8 (extension: not in the reference; include/cfx.h "MXINT8") -----------------------------------------------
+def quantize_mxint8(input_tensor: torch.Tensor):
+    """-> codes (N, C) int8 [q = clamp(rne(x * 2^(6-X)), -127, 127)], scales (N, C/32) uint8 [one E8M0 byte X + 127 per block of 32
+    consecutive elements of a row; 0xFF: a block with a NaN or an inf].  The native MXINT8 wire codec at residual 0."""
+    x = _nc(input_tensor)
+    N, C = x.shape
+    assert C % 64 == 0, f"Dimension C (1) size must be a multiple of 64 for MXINT8 blocks, got {C}"
+    pkt, _ = codecs.compress(K.MXINT8, x, None, N, C, update_cache=False)
+    by = pkt.view(torch.uint8)
+    return by[:N * C].view(torch.int8).view(N, C), by[N * C:].view(N, C // 32)
+
+
+def dequantize_mxint8(codes: torch.Tensor, scales: torch.Tensor):
+    assert codes.dtype == torch.int8 and scales.dtype == torch.uint8
+    N, C = codes.shape
+    assert scales.shape == (N, C // 32)
+    return codecs.decompress(K.MXINT8, _cat_packet(codes, scales), None, N, C)
+
+
+def sim_mxint8(input_tensor: torch.Tensor):
+    return dequantize_mxint8(*quantize_mxint8(input_tensor))
+
+
 def sim_int4(input_tensor: torch.Tensor, dim):
     x = _nc(input_tensor)
     if dim == 1:

@@ -22,7 +22,7 @@ Semantics kept from the reference (file:line = xfuser/compact/main.py):
   log_compress_stats: `cfx_residual2_delta` / `cfx_residual2_update` around the codec; states in place either way); `simulate` ships the dequantised tensor (:117-119, :126-127); the fastpath accepts
   only BINARY / INT2 (:131, :277).
 
-Activations may be fp16 or bf16.  bf16 (what FLUX, CogVideoX, HunyuanVideo run in) is served by the 1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs - plus WARMUP and
+Activations may be fp16 or bf16.  bf16 (what FLUX, CogVideoX, HunyuanVideo run in) is served by the 1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs and MXINT8 - plus WARMUP and
 IDENTITY - with first-order or no residuals: states and reconstructions are bf16, the residual and the wire stay fp16 (include/cfx.h,
 "bf16 activations").  Every other combination with bf16 raises NotImplementedError before any state is touched
 (`_check_bf16`); nothing is ever cast behind the caller's back.  `compact_decompress` with residual 0 has no state to take the element
@@ -173,6 +173,8 @@ def _native(compress_type: T) -> Tuple[int, int]:
         return int(codecs.Codec.INT2_BLOCK), int(_settings.get("int2_block"))
     if compress_type == T.INT3_BLOCK:
         return int(codecs.Codec.INT3_BLOCK), int(_settings.get("int3_block"))
+    if compress_type == T.MXINT8:
+        return int(codecs.Codec.MXINT8), 0
     if compress_type == T.SPARSE:
         assert _config.sparse_ratio is not None, "sparse_ratio must be provided for SPARSE compression"
         return int(codecs.Codec.TOPK), int(_config.sparse_ratio)
@@ -189,10 +191,10 @@ def _check_bf16(dtype, compress_type: T) -> None:
     cfg = _config
 
     def no(option: str):
-        raise NotImplementedError(f"torch.bfloat16 activations are not supported with {option}: bf16 runs with BINARY (comp_rank -1) / INT2 / BINARY_BLOCK / INT2_BLOCK / INT3_BLOCK / "
+        raise NotImplementedError(f"torch.bfloat16 activations are not supported with {option}: bf16 runs with BINARY (comp_rank -1) / INT2 / BINARY_BLOCK / INT2_BLOCK / INT3_BLOCK / MXINT8 / "
                                   "WARMUP / IDENTITY, compress_residual 0 or 1, no simulation, no quantized cache - use fp16 activations "
                                   "for anything else")
-    if compress_type not in (T.BINARY, T.INT2, T.BINARY_BLOCK, T.INT2_BLOCK, T.INT3_BLOCK, T.WARMUP, T.IDENTITY):
+    if compress_type not in (T.BINARY, T.INT2, T.BINARY_BLOCK, T.INT2_BLOCK, T.INT3_BLOCK, T.MXINT8, T.WARMUP, T.IDENTITY):
         no(f"compress type {getattr(compress_type, 'name', compress_type)}")
     if compress_type == T.BINARY and cfg.comp_rank is not None and cfg.comp_rank != -1:
         no(f"BINARY with comp_rank {cfg.comp_rank} (rank-K scales)")

@@ -32,6 +32,8 @@ _CODECS = {
     "int3block32": (T.INT3_BLOCK, -1, False),
     "int3block64": (T.INT3_BLOCK, -1, False),
     "int3block128": (T.INT3_BLOCK, -1, False),
+    # extension: the block-scaled OCP Microscaling int8 codec (blocks of 32 by the format: no switch)
+    "mxint8": (T.MXINT8, -1, False),
 }
 # method -> PatchConfig arguments (use_compact, async_comm, async_warmup = the warm-up steps unless given)     configs.py:110-165
 _PATCH = {"int2patch": (True, False, None), "df": (False, True, None), "patch": (False, False, 0)}

@@ -4,7 +4,7 @@
 BINARY `[codes | U(N,1) | V(1,C)]` and SPARSE `[val | idx]` are single native launches; LOW_RANK / LOW_RANK_Q are in
 `lowrank.py`.  INT2 / INT4 / INT8 / IDENTITY are not slowpath wire codecs in the reference (ValueError, :80-81);
 here INT2 / INT4 / INT8 are accepted as an extension because BASELINE.json's configs use them as residual codecs, and
-INT2_MINMAX (simulation-only in the reference) as the native 4-level wire codec; MXFP4 (not in the reference) is the native block-scaled codec 8.
+INT2_MINMAX (simulation-only in the reference) as the native 4-level wire codec; MXFP4 and MXINT8 (not in the reference) are the native block-scaled codecs 8 and 16.
 BINARY_BLOCK (native codec 10), INT2_BLOCK (native codec 12) and INT3_BLOCK (native codec 14) are no slowpath wire codecs: their block size is a host switch, not an
 argument of these functions (ValueError)."""
 from __future__ import annotations
@@ -16,7 +16,7 @@ from .compress_topk import SPARSE_LAST_DIM_SIZE  # noqa: F401
 from .utils import COMPACT_COMPRESS_TYPE as T
 
 _MAP = {T.BINARY: codecs.Codec.BINARY, T.INT2: codecs.Codec.INT2, T.INT4: codecs.Codec.INT4, T.INT8: codecs.Codec.INT8,
-        T.SPARSE: codecs.Codec.TOPK, T.INT2_MINMAX: codecs.Codec.INT2_MINMAX, T.MXFP4: codecs.Codec.MXFP4}
+        T.SPARSE: codecs.Codec.TOPK, T.INT2_MINMAX: codecs.Codec.INT2_MINMAX, T.MXFP4: codecs.Codec.MXFP4, T.MXINT8: codecs.Codec.MXINT8}
 
 
 def _resolve(compress_type, rank, sparse_ratio):

@@ -26,7 +26,7 @@ class COMPACT_COMPRESS_TYPE(Enum):
     OCP Microscaling codec (native codec 8), and BINARY_BLOCK, the block-scaled 1-bit codec (native codec 10; its block size is the host
     switch compactfusion_amd.configure(binary_block=32|64|128)), and INT2_BLOCK, the block-scaled 2-bit codec (native codec 12; block size:
     configure(int2_block=32|64|128)), and INT3_BLOCK, the block-scaled 3-bit codec (native codec 14; block size:
-    configure(int3_block=32|64|128)), which the reference does not have."""
+    configure(int3_block=32|64|128)), and MXINT8, the block-scaled OCP Microscaling int8 codec (native codec 16), which the reference does not have."""
 
     WARMUP = "warmup"
     SPARSE = "sparse"
@@ -43,6 +43,7 @@ class COMPACT_COMPRESS_TYPE(Enum):
     BINARY_BLOCK = "binary-block"   # extension (not in the reference enum)
     INT2_BLOCK = "int2-block"       # extension (not in the reference enum)
     INT3_BLOCK = "int3-block"       # extension (not in the reference enum)
+    MXINT8 = "mxint8"               # extension (not in the reference enum)
 
 
 class CompactConfig:
@@ -105,7 +106,7 @@ class CompactConfig:
 
 
 class CompactCache:
-    """key -> persistent (N, C) state buffer in the activations' element type - fp16, or bf16 with the 1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit exchange - (+ optional
+    """key -> persistent (N, C) state buffer in the activations' element type - fp16, or bf16 with the 1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit and MXINT8 exchange - (+ optional
     second-order `delta_base`).
 
     `put` copies into the key's arena buffer unless it is handed that very buffer (what the in-place kernels do), so

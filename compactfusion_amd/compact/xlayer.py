@@ -3,7 +3,7 @@
 What the reference does per layer and denoise step in Python (xfuser/compact/main.py:390-420 `compact_all_gather`: compress, list
 all-gather, W decompress calls; patchpara/fwd.py:88-102; ring.py:188-206 + 265-269: compress K and V, W-1 relay hops, a
 decompress per hop) is here ONE host call into libcfx per layer: `cfx_plan_add_exchange_layer[_p2p]` replayed by `cfx_plan_run_x`
-(include/cfx.h).  For every streaming codec (1-bit, 2-bit, int4, int8, top-k, 4-level min/max, MXFP4, block-scaled 1-bit, 2-bit and 3-bit) that is ONE codec launch whose reconstruction workgroups wait, state
+(include/cfx.h).  For every streaming codec (1-bit, 2-bit, int4, int8, top-k, 4-level min/max, MXFP4, block-scaled 1-bit, 2-bit and 3-bit, MXINT8) that is ONE codec launch whose reconstruction workgroups wait, state
 tiles already in registers, for the packets' arrival - and in the peer-to-peer transport the exchange itself (publish this rank's word, await
 the peers') runs inside that launch; top-k and shapes without the one-launch form run the same work in stream order
 (compress ; exchange ; reconstruct) - same results, still one host call.
@@ -401,13 +401,13 @@ class LayerOp:
         # per tensor and one reconstruction per peer tensor from Python (16 launches and 0.44 ms of host time per FLUX layer).
         self.lowrank = self.cid >= 100
         self.quantized = self.cid == 102
-        # element type of the layer: the states' (fp16, or bf16 with the 1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit codecs - include/cfx.h, "bf16 activations"); the
+        # element type of the layer: the states' (fp16, or bf16 with the 1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit codecs and MXINT8 - include/cfx.h, "bf16 activations"); the
         # activations of every run must have it.  `cabi` is the C-ABI's codec argument: the id, with CFX_ELEM_BF16 for bf16
         self.dtype = codecs.elem_dtype(*self.own, *[t for _, ks, vs in self.peers for t in (ks, vs)])
         if self.dtype == torch.bfloat16 and self.cid not in (int(codecs.Codec.BINARY), int(codecs.Codec.INT2), int(codecs.Codec.BINARY_BLOCK), int(codecs.Codec.INT2_BLOCK),
-                                                              int(codecs.Codec.INT3_BLOCK)):
+                                                              int(codecs.Codec.INT3_BLOCK), int(codecs.Codec.MXINT8)):
             raise NotImplementedError(f"torch.bfloat16 activations are not supported with codec id {self.cid} in the layer exchange op "
-                                      "(bf16 runs with the 1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs)")
+                                      "(bf16 runs with the 1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs and MXINT8)")
         self.cabi = self.cid if self.lowrank else codecs.codec_arg(self.cid, self.dtype)
         self.own2 = None if own_second is None else list(own_second)
         self.peer2 = [] if own_second is None else [tuple(p) for p in (peer_second or [])]
@@ -894,4 +894,4 @@ class LayerOp:
 def usable(cid: int, world: int, is_cuda: bool, ef: bool = True) -> bool:
     """Can the layer's exchange run as a LayerOp: a native streaming codec - or the low-rank family with error feedback -, W ranks whose
     2 (W - 1) peer tensors + own K,V fit one batch."""
-    return is_cuda and (cid in (1, 2, 3, 4, 5, 6, 8, 10, 12, 14) or (cid in (101, 102) and ef)) and 2 * (world - 1) + 2 <= MAX_ITEMS
+    return is_cuda and (cid in (1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16) or (cid in (101, 102) and ef)) and 2 * (world - 1) + 2 <= MAX_ITEMS

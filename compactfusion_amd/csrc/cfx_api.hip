@@ -199,7 +199,8 @@ static bool shape_ok(int codec, int N, int C, int param) {
         case CFX_CODEC_INT4: return N % 2 == 0;
         case CFX_CODEC_INT8: return true;
         case CFX_CODEC_INT2_MINMAX: return N % 4 == 0;
-        case CFX_CODEC_MXFP4: return C % 64 == 0 && param == 0;
+        case CFX_CODEC_MXFP4:
+        case CFX_CODEC_MXINT8: return C % 64 == 0 && param == 0;
         case CFX_CODEC_BINARY_BLOCK:
         case CFX_CODEC_INT2_BLOCK:
         case CFX_CODEC_INT3_BLOCK: return (param == 32 || param == 64 || param == 128) && C % (param > 64 ? param : 64) == 0;
@@ -454,6 +455,7 @@ size_t cfx_packet_bytes(int codec, int N, int C, int param) {
         case CFX_CODEC_BINARY_BLOCK: return n * c / 8 + 2 * (n * c / param);
         case CFX_CODEC_INT2_BLOCK: return n * c / 4 + 2 * (n * c / param);
         case CFX_CODEC_INT3_BLOCK: return n * c / 4 + n * c / 8 + 2 * (n * c / param);
+        case CFX_CODEC_MXINT8: return n * c + n * c / 32;
         case CFX_CODEC_TOPK: return 2 * (n * c / param) + n * c / (2 * param);
     }
     return 0;
@@ -523,6 +525,7 @@ int cfx_i_decompress_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int para
         case CFX_CODEC_BINARY_BLOCK: return cfx_i_bb_decompress(ctx, bf16, N, C, param, batch, b, stream, pre, pre_val);
         case CFX_CODEC_INT2_BLOCK: return cfx_i_i2b_decompress(ctx, bf16, N, C, param, batch, b, stream, pre, pre_val);
         case CFX_CODEC_INT3_BLOCK: return cfx_i_i3b_decompress(ctx, bf16, N, C, param, batch, b, stream, pre, pre_val);
+        case CFX_CODEC_MXINT8: return cfx_i_mxi8_decompress(ctx, bf16, N, C, batch, b, stream, pre, pre_val);
         default: return cfx_i_topk_decompress(ctx, N, C, param, batch, b, stream, pre, pre_val);
     }
 }
@@ -691,6 +694,7 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     if (codec == CFX_CODEC_BINARY_BLOCK) return cfx_i_bb_compress(cc);
     if (codec == CFX_CODEC_INT2_BLOCK) return cfx_i_i2b_compress(cc);
     if (codec == CFX_CODEC_INT3_BLOCK) return cfx_i_i3b_compress(cc);
+    if (codec == CFX_CODEC_MXINT8) return cfx_i_mxi8_compress(cc);
 
     // statistics + finalize: ONE launch with the in-launch finalize (default), or the two-kernel sequence
     const bool fused = ctx->fused && CB <= TICK_MAX_CB;

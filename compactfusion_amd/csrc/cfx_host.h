@@ -1,5 +1,5 @@
 // Host-side internals shared by the translation units of libcfx.so's streaming codecs (cfx_api.hip: context, C-ABI, dispatch; cfx_absmean.hip,
-// cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip, cfx_i2block.hip, cfx_i3block.hip: each family's kernels AND the code that launches them; cfx_local.h: the launch
+// cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip, cfx_i2block.hip, cfx_i3block.hip, cfx_mxint8.hip: each family's kernels AND the code that launches them; cfx_local.h: the launch
 // skeleton the last three - the block-local codecs - share).  Not part of the ABI.
 #ifndef CFX_HOST_H
 #define CFX_HOST_H
@@ -35,6 +35,7 @@ CFX_HIDDEN int cfx_i_mx_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_bb_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_i2b_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_i3b_compress(CompressCall& cc);
+CFX_HIDDEN int cfx_i_mxi8_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_absmean_compress(CompressCall& cc);
 CFX_HIDDEN int cfx_i_minmax_compress(CompressCall& cc);
 // reconstruction launches of a validated batch (decompress_impl's dispatch); `pre` / `pre_val`: an optional flag word the kernel waits for
@@ -46,6 +47,7 @@ CFX_HIDDEN int cfx_i_mx_decompress(cfx_ctx* ctx, int N, int C, int batch, const 
 CFX_HIDDEN int cfx_i_bb_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_i2b_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
 CFX_HIDDEN int cfx_i_i3b_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
+CFX_HIDDEN int cfx_i_mxi8_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
 // cfx_api.hip
 CFX_HIDDEN int cfx_i_auto_rows(const cfx_ctx* ctx, int N, int C, int batch, bool stats);
 CFX_HIDDEN int cfx_i_fused_rows(const cfx_ctx* ctx, int N, int C, int batch, int cus);

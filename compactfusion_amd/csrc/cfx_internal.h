@@ -176,14 +176,16 @@ static inline int codec_id(int codec_arg, bool* bf16) {
     const int id = codec_arg & 0xff;
     *bf16 = (codec_arg & CFX_ELEM_BF16) != 0;
     if (codec_arg < 0 || (codec_arg & ~(0xff | CFX_ELEM_BF16))) return 0;
-    if (*bf16 && id != CFX_CODEC_BINARY && id != CFX_CODEC_INT2 && id != CFX_CODEC_BINARY_BLOCK && id != CFX_CODEC_INT2_BLOCK && id != CFX_CODEC_INT3_BLOCK) return 0;
+    if (*bf16 && id != CFX_CODEC_BINARY && id != CFX_CODEC_INT2 && id != CFX_CODEC_BINARY_BLOCK && id != CFX_CODEC_INT2_BLOCK && id != CFX_CODEC_INT3_BLOCK &&
+        id != CFX_CODEC_MXINT8)
+        return 0;
     return id;
 }
 
-// the streaming codecs' ids (include/cfx.h enum cfx_codec; 7, 9, 11 and 13 are not)
+// the streaming codecs' ids (include/cfx.h enum cfx_codec; 7, 9, 11, 13 and 15 are not)
 static inline bool codec_known(int id) {
     return (id >= CFX_CODEC_BINARY && id <= CFX_CODEC_INT2_MINMAX) || id == CFX_CODEC_MXFP4 || id == CFX_CODEC_BINARY_BLOCK || id == CFX_CODEC_INT2_BLOCK ||
-           id == CFX_CODEC_INT3_BLOCK;
+           id == CFX_CODEC_INT3_BLOCK || id == CFX_CODEC_MXINT8;
 }
 
 // ---------------------------------------------------------------------------------------------------

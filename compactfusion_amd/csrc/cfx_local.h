@@ -1,4 +1,4 @@
-// The launch skeleton of libcfx.so's BLOCK-LOCAL wire codecs - top-k (cfx_topk.hip), MXFP4 (cfx_mx.hip), BINARY_BLOCK (cfx_bblock.hip), INT2_BLOCK (cfx_i2block.hip), INT3_BLOCK (cfx_i3block.hip): a
+// The launch skeleton of libcfx.so's BLOCK-LOCAL wire codecs - top-k (cfx_topk.hip), MXFP4 (cfx_mx.hip), BINARY_BLOCK (cfx_bblock.hip), INT2_BLOCK (cfx_i2block.hip), INT3_BLOCK (cfx_i3block.hip), MXINT8 (cfx_mxint8.hip): a
 // block's packet words are a function of the block alone, so nothing global is waited for.  Held once here: the bodies of the stand-alone
 // compress / decompress kernels and of the one-launch layer (LOCAL_LAYER), and the host code of the layer form (decision, gate bookkeeping,
 // hand-over to an exchange-layer op).  A family file keeps its codec - a policy type P - and its __global__ kernels, one-line wrappers of these bodies:

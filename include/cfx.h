@@ -43,6 +43,8 @@
  *           (no wire in the reference: INT2's sign / magnitude levels around BINARY_BLOCK's block scale)
  *   INT3_BLOCK [ hi N*C/4 B : 2-bit (sign<<1 | mag>>1), INT2's code layout | lo N*C/8 B : bit = mag & 1, BINARY's bit layout | scale N*C/B fp16 : row-major, one per block ]
  *           (no wire in the reference: a sign and four magnitude levels around BINARY_BLOCK's block scale)
+ *   MXINT8  [ codes N*C B : element j of the flat view at byte j, two's complement | scale N*C/32 B : one E8M0 byte per block, row-major ]
+ *           (no wire in the reference: the OCP Microscaling format, blocks of 32 consecutive elements of a row)
  *   The sections after the first start at the byte offsets these sizes give: they need not be 16-byte aligned (int8 with C % 16 == 8
  *   and N odd, int4 with C % 16 == 8 and N/2 odd, INT2_MINMAX with C % 16 == 8 and N/4 odd, 1-bit / 2-bit whenever N*C/8 resp. N*C/4 is not a multiple of 16).
  *   INT4 `min` of a channel whose minimum is zero: where zeros of BOTH signs occur among the channel's deltas, `min` may hold either zero
@@ -151,9 +153,37 @@
  *   one-launch layer k_i3b_layer (id 31) under k_i2b_layer's conditions; otherwise, and under stream capture, compress ; (exchange) ;
  *   decompress in stream order with the same results.  Refused, as for INT2_BLOCK: the second-order entry points and
  *   cfx_plan_set_second_order (CFX_ERR_CODEC: residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items
- *   (CFX_ERR_CODEC), any other high bit on the codec argument (CFX_ERR_CODEC, sizes 0).  Ids 13 and 15 are no codecs.
+ *   (CFX_ERR_CODEC), any other high bit on the codec argument (CFX_ERR_CODEC, sizes 0).  Ids 13 and 15 are no codecs (17 is none).
  *
- * bf16 activations (CFX_CODEC_BINARY, CFX_CODEC_INT2, CFX_CODEC_BINARY_BLOCK, CFX_CODEC_INT2_BLOCK and CFX_CODEC_INT3_BLOCK only)
+ * MXINT8 (CFX_CODEC_MXINT8 = 16, param 0; any other param: CFX_ERR_SHAPE, sizes 0): the OCP Microscaling (MX v1.0) INT8 element - an
+ *   int8 with an implied 2^-6 - under one E8M0 power-of-two scale per 32 consecutive elements of a row (C % 32 == 0: also blocks of the
+ *   flat view), with MXFP4's floor scale and a lower clamp on the shared exponent so that decode never leaves fp16.  A block's scale is
+ *   a function of that block alone: one streaming pass, no statistic to wait for, no workspace.  Bit for bit, one rounding per line:
+ *       d      = fp16(x - base)                                   (base NULL: x;  bf16: "bf16 activations" below)
+ *       a      = max over the block of (bits(d) & 0x7fff)         (integer max: the largest magnitude)
+ *       a >= 0x7c00 (a NaN or an inf in the block): scale byte 0xFF, all 32 code bytes 0, every element of the block reconstructs to NaN (0x7e00)
+ *       e      = floor(log2 |d|max)                               (normal: (a >> 10) - 15; subnormal: from the leading bit; a == 0: below the clamp)
+ *       X      = max(e, -18)      scale byte = X + 127            (so X in [-18, 15], bytes 109 ... 142)
+ *       y      = d * 2^(6 - X)                                    (exact in fp32: an 11-bit significand times a power of two; |y| < 128)
+ *       q      = clamp( round-to-nearest-even(y), -127, 127 )     (symmetric: -128 is never sent)
+ *       code   = q as a two's-complement byte                     (a -0 or a negative delta that rounds to 0 sends 0x00)
+ *       recv   = q * 2^(X - 6)                                    (exact in fp16: |q| <= 127 times a power of two >= 2^-24 - what the clamp at -18
+ *                                                                 buys; |recv| <= 65024; q == 0 gives +0, bits 0x0000)
+ *       new_base = recon = fp16(base + recv)                      (base NULL: recv, bits verbatim;  CFX_FLAG_NO_EF: new_base = x)
+ *   So |d - recv| <= 2^(X-7) wherever |y| <= 127.5 and <= (15/16) 2^(X-6) otherwise (saturation: only the top 1/128 of a binade), and a
+ *   block with |d|max < 2^-17 is reproduced exactly.  A receiver reads the byte 0x80 as -127; a scale byte outside 109 ... 142 other than
+ *   0xFF is never sent and its result is unspecified.  Wire: two sections, no padding -
+ *       codes N*C bytes     element j of the flat view at byte j
+ *       scale N*C/32 bytes  block k at byte N*C + k
+ *   Shapes: C % 64 == 0, any N >= 1; cfx_packet_bytes = N*C + N*C/32 (8.25 bits per element); cfx_workspace_bytes is 0: callers pass
+ *   NULL / 0.  CFX_ELEM_BF16 is accepted (codec argument 0x110) under the "bf16 activations" rules below.  Forms: stand-alone compress /
+ *   decompress (they report top-k's kernel ids, 13 and 14) and the one-launch layer k_mxi8_layer (the gated layer id, 31), taken under
+ *   k_mx_layer's conditions; otherwise, and under stream capture, compress ; (exchange) ; decompress in stream order with the same
+ *   results.  Refused, as for the other block-local codecs: the second-order entry points and cfx_plan_set_second_order (CFX_ERR_CODEC:
+ *   residual 2 composes cfx_residual2_delta / _update around the codec), ride-along items (CFX_ERR_CODEC), any other high bit on the
+ *   codec argument (CFX_ERR_CODEC, sizes 0).
+ *
+ * bf16 activations (CFX_CODEC_BINARY, CFX_CODEC_INT2, CFX_CODEC_BINARY_BLOCK, CFX_CODEC_INT2_BLOCK, CFX_CODEC_INT3_BLOCK and CFX_CODEC_MXINT8 only)
  *   CFX_ELEM_BF16 or-ed into the `codec` argument of an entry point that takes one (cfx_packet_bytes, cfx_workspace_bytes,
  *   cfx_compress[_batch[_ex|_gated]], cfx_decompress[_batch], cfx_plan_add_compress[_ex|_gated], cfx_plan_add_decompress,
  *   cfx_plan_add_exchange_layer[_p2p], and through them cfx_plan_copy_op) says that ALL tensor operands of the call - x, base, new_base,
@@ -161,7 +191,7 @@
  *   CFX_FLAG_ELEM_BF16 in `flags`.  The residual domain and the wire stay fp16:
  *       d        = fp16_rne( fp32(x) - fp32(base) )          one fp32 subtraction, one rounding to fp16; base NULL: d = fp16_rne(fp32(x))
  *       d -> recv  exactly the fp16 path: sign bits / 2-bit codes, exact sums in units of 2^-24, fp16 scales, packet bytes;
- *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels  or +-s of the block (BINARY_BLOCK)  or the block's two / four levels (INT2_BLOCK / INT3_BLOCK), in fp16
+ *                  recv = (2b - 1) * fp16(u * v)  or the 2-bit levels  or +-s of the block (BINARY_BLOCK)  or the block's two / four levels (INT2_BLOCK / INT3_BLOCK)  or q * 2^(X-6) (MXINT8), in fp16
  *       new_base = recon = bf16_rne( fp32(base) + fp32(recv) )     base NULL: bf16_rne(fp32(recv))
  *       CFX_FLAG_NO_EF: new_base = x, copied verbatim as bf16 bits
  *   Packet layout, cfx_packet_bytes and cfx_workspace_bytes are those of the fp16 codec: a bf16 sender's packet is a valid fp16-path
@@ -187,14 +217,14 @@
  *   In place is allowed: new_base == base, new_delta_base == delta_base.  base and delta_base are required (CFX_ERR_NULL); a
  *   reconstruction item may have new_delta_base NULL (update_cache = False: recon only); a compress item needs new_base and
  *   new_delta_base with CFX_FLAG_UPDATE_CACHE and writes only the packet without it.  CFX_ERR_CODEC before any launch: CFX_FLAG_NO_EF
- *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6, 8, 10, 12 and 14 (those compose cfx_residual2_delta / _update
+ *   (main.py ignores error_feedback with residual 2), CFX_ELEM_BF16, codec ids 3 - 6, 8, 10, 12, 14 and 16 (those compose cfx_residual2_delta / _update
  *   around the codec).  The second-order launches report the kernel ids of their first-order twins (cfx_profile_enable).
  *
  * Non-finite input (NaN, +-inf in x or base, or an x - base that overflows or is inf - inf)
  *   INT4 / INT8 / INT2_MINMAX: the per-channel min and max propagate NaN as the reference's torch.min / torch.max do - a channel with a NaN delta gets
  *                a NaN scale (and min), codes 0, zero point 0 and a NaN reconstruction; +-inf flow through the fp16 arithmetic.
  *   TOPK:        |delta| is ranked as the reference's tl.argmax ranks it: NaN above everything, +inf included; the first NaN wins.
- *   MXFP4:       a block with a NaN or an inf delta is the 0xFF block above (codes 0, NaN reconstruction); its neighbours are untouched.
+ *   MXFP4, MXINT8: a block with a NaN or an inf delta is the 0xFF block above (codes 0, NaN reconstruction); its neighbours are untouched.
  *   BINARY / INT2 / BINARY_BLOCK / INT2_BLOCK / INT3_BLOCK: unspecified.  Their scales are exact integer sums of |delta| (cfx_device.h habs_units), which cannot carry inf or
  *                NaN; the outputs are finite garbage or NaN, and need not match the reference.
  */
@@ -237,9 +267,10 @@ enum cfx_codec {
     CFX_CODEC_MXFP4 = 8,     /* COMPACT_COMPRESS_TYPE.MXFP4: FP4 E2M1 elements, one E8M0 scale per 32 of a row; param 0 (7 is no codec) */
     CFX_CODEC_BINARY_BLOCK = 10, /* COMPACT_COMPRESS_TYPE.BINARY_BLOCK: sign bits, one fp16 abs-mean per param = 32 / 64 / 128 of a row (9 is no codec) */
     CFX_CODEC_INT2_BLOCK = 12, /* COMPACT_COMPRESS_TYPE.INT2_BLOCK: INT2's codes, one fp16 abs-mean per param = 32 / 64 / 128 of a row (11 is no codec) */
-    CFX_CODEC_INT3_BLOCK = 14 /* COMPACT_COMPRESS_TYPE.INT3_BLOCK: sign + 2 magnitude bits, one fp16 abs-mean per param = 32 / 64 / 128 of a row (13 is no codec) */
+    CFX_CODEC_INT3_BLOCK = 14, /* COMPACT_COMPRESS_TYPE.INT3_BLOCK: sign + 2 magnitude bits, one fp16 abs-mean per param = 32 / 64 / 128 of a row (13 is no codec) */
+    CFX_CODEC_MXINT8 = 16    /* COMPACT_COMPRESS_TYPE.MXINT8: int8 elements (implied 2^-6), one E8M0 scale per 32 of a row; param 0 (15 is no codec) */
 };
-/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs; "bf16 activations" above) */
+/* or-ed into a `codec` argument: the call's tensors are bf16 (1-bit, 2-bit, block-scaled 1-bit / 2-bit / 3-bit codecs and MXINT8; "bf16 activations" above) */
 #define CFX_ELEM_BF16 0x100
 
 enum cfx_flags {

@@ -2,8 +2,9 @@
 """PMC driver (developer tool): one BASELINE configuration's codec launches, a few repetitions over distinct (cold) tensors, plus the 96 MiB copy
 probe for calibration - run under `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (separate passes; tools/collect_profiles.sh), summarised by
 tools/pmc_summary.py + tools/codec_pmc_table.py into profiles/r04_pmc_traffic_codecs.json.
-usage: python tools/codec_pmc_run.py <config 1|2|3|3b|4|5|2m|3m|4m|2x|3x|2k|3k|3k32|3k128|2q|3q|3q32|3q128|2t|3t|3t32|3t128> <form layer|launches>     (2m / 3m / 4m: INT2_MINMAX at the shards of 2 / 3 / 4; 2x / 3x: MXFP4 at the shards of 2 / 3;
-  2k / 3k: BINARY_BLOCK with blocks of 64 at the shards of 2 / 3, 3k32 / 3k128: blocks of 32 / 128; 2q / 3q / 3q32 / 3q128: the same for INT2_BLOCK; 2t / 3t / 3t32 / 3t128: for INT3_BLOCK)
+usage: python tools/codec_pmc_run.py <config 1|2|3|3b|4|5|2m|3m|4m|2x|3x|2k|3k|3k32|3k128|2q|3q|3q32|3q128|2t|3t|3t32|3t128|1y|2y|3y> <form layer|launches>     (2m / 3m / 4m: INT2_MINMAX at the shards of 2 / 3 / 4; 2x / 3x: MXFP4 at the shards of 2 / 3;
+  2k / 3k: BINARY_BLOCK with blocks of 64 at the shards of 2 / 3, 3k32 / 3k128: blocks of 32 / 128; 2q / 3q / 3q32 / 3q128: the same for INT2_BLOCK; 2t / 3t / 3t32 / 3t128: for INT3_BLOCK;
+  1y / 2y / 3y: MXINT8 at config 1's tensor and the shards of 2 / 3)
   layer     what the library runs by default (min/max codecs on small shards: k_minmax_layer; 1-bit / 2-bit: the gated layer launch)
   launches  cfx_set_gated_launch(ctx, 0): statistics + finalize ; quantise (+ error feedback) ; reconstruction as separate launches
 Counter passes SERIALISE dispatches, so everything here is loop-back on ONE stream (no flag kernel on another stream)."""
@@ -19,7 +20,8 @@ CFG = {  # codec id, param, (N, C), tensors compressed per layer, tensors recons
     "2x": (8, 0, (1024, 1152), 2, 4), "3x": (8, 0, (544, 3072), 2, 16),
     "3k32": (10, 32, (544, 3072), 2, 16), "3k": (10, 64, (544, 3072), 2, 16), "3k128": (10, 128, (544, 3072), 2, 16), "2k": (10, 64, (1024, 1152), 2, 4),
     "3q32": (12, 32, (544, 3072), 2, 16), "3q": (12, 64, (544, 3072), 2, 16), "3q128": (12, 128, (544, 3072), 2, 16), "2q": (12, 64, (1024, 1152), 2, 4),
-    "3t32": (14, 32, (544, 3072), 2, 16), "3t": (14, 64, (544, 3072), 2, 16), "3t128": (14, 128, (544, 3072), 2, 16), "2t": (14, 64, (1024, 1152), 2, 4)}
+    "3t32": (14, 32, (544, 3072), 2, 16), "3t": (14, 64, (544, 3072), 2, 16), "3t128": (14, 128, (544, 3072), 2, 16), "2t": (14, 64, (1024, 1152), 2, 4),
+    "1y": (16, 0, (4096, 1152), 1, 1), "2y": (16, 0, (1024, 1152), 2, 4), "3y": (16, 0, (544, 3072), 2, 16)}
 cfg, form = sys.argv[1], sys.argv[2]
 cid, param, (N, C), ncomp, nrec = CFG[cfg]
 lib, ctx = _lib.load(), K.context(0)

@@ -69,6 +69,11 @@ CONFIGS = [
     ("11d FLUX.1 1024^2 ring 8, INT3_BLOCK B=32 bf16 (config 3's shard)", 0x10E, 32, (544, 3072), 57, 2, 14, True),
     ("11e FLUX.1 1024^2 ring 8, INT3_BLOCK B=64 bf16 (config 3's shard)", 0x10E, 64, (544, 3072), 57, 2, 14, True),
     ("11f FLUX.1 1024^2 ring 8, INT3_BLOCK B=128 bf16 (config 3's shard)", 0x10E, 128, (544, 3072), 57, 2, 14, True),
+    # the block-scaled 8-bit codec (MXINT8, codec 16, param 0; 0x110: bf16): int8's class of error with no statistic to wait for
+    ("12a FLUX.1 1024^2 ring 8, MXINT8 (config 3's shard)", 16, 0, (544, 3072), 57, 2, 14, True),
+    ("12b FLUX.1 1024^2 ring 8, MXINT8 bf16 (config 3's shard)", 0x110, 0, (544, 3072), 57, 2, 14, True),
+    ("12c MXINT8 residual [1,4096,1152], world 1 (config 1's tensor)", 16, 0, (4096, 1152), 1, 1, 1, True),
+    ("12d PixArt-a 512^2 SP2 patch-gather MXINT8 (config 2's shard)", 16, 0, (1024, 1152), 28, 2, 4, False),
 ]
 NAMES = {1: "binary", 2: "int2", 3: "int4", 4: "int8", 5: "topk"}
 # algorithmic bytes per element (compress + error feedback, reconstruct); low-rank: x + state in, state out (6), state in / out (4)
@@ -77,8 +82,11 @@ ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (6 +
 
 def alg_pair(cid, param=0):
     """(compress + error feedback, reconstruct) bytes per element of a codec argument; the block-scaled 1-bit / 2-bit / 3-bit codecs: 1/8,
-    1/4 resp. 3/8 + 2/B of packet"""
+    1/4 resp. 3/8 + 2/B of packet; MXINT8: 1 + 1/32"""
     cid &= 0xff
+    if cid == 16:
+        pkt = 1 + 1.0 / 32
+        return 6 + pkt, 4 + pkt
     if cid in (10, 12, 14):
         pkt = {10: 0.125, 12: 0.25, 14: 0.375}[cid] + 2.0 / param
         return 6 + pkt, 4 + pkt
@@ -215,7 +223,7 @@ def gpu_step(cid, param, N, C, L, ncomp, nrec, update, min_steps=20, budget_s=0.
 
 
 def cpu_step(cid, param, N, C, L, ncomp, nrec, update, budget=8.0):
-    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4, BINARY_BLOCK, INT2_BLOCK, INT3_BLOCK, bf16
+    if cid not in NAMES:          # no C restatement: the low-rank family, INT2_MINMAX, MXFP4, BINARY_BLOCK, INT2_BLOCK, INT3_BLOCK, MXINT8, bf16
         return None, 0
     from oracle import c_oracle as CO
     name = NAMES[cid]
