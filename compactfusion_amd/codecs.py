@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 from enum import IntEnum
-from typing import Callable, Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -28,6 +28,27 @@ class Codec(IntEnum):
     INT3_BLOCK = 14     # residual sign + 2 magnitude bits (four levels) with one fp16 abs-mean per param = 32 / 64 / 128 of a row (include/cfx.h "INT3_BLOCK"); 13 is no codec
     MXINT8 = 16         # residual int8 elements (implied 2^-6) with one E8M0 scale per 32 of a row (OCP Microscaling; include/cfx.h "MXINT8"); 15 is no codec
 
+
+class CodecRow(NamedTuple):
+    bf16: bool                   # bf16 tensors: CFX_ELEM_BF16 on the codec argument (include/cfx.h, "bf16 activations")
+    setting: Optional[str]       # the compactfusion_amd.configure() switch that supplies the codec's param; None: no such switch
+
+
+# What the Python layers know about each streaming codec; the library's own table is codec_table in csrc/cfx_api.hip
+# (tests/test_codec_table.py holds the two together)
+CODEC_TABLE = {
+    Codec.BINARY: CodecRow(True, None),
+    Codec.INT2: CodecRow(True, None),
+    Codec.INT4: CodecRow(False, None),
+    Codec.INT8: CodecRow(False, None),
+    Codec.TOPK: CodecRow(False, None),
+    Codec.INT2_MINMAX: CodecRow(False, None),
+    Codec.MXFP4: CodecRow(False, None),
+    Codec.BINARY_BLOCK: CodecRow(True, "binary_block"),
+    Codec.INT2_BLOCK: CodecRow(True, "int2_block"),
+    Codec.INT3_BLOCK: CodecRow(True, "int3_block"),
+    Codec.MXINT8: CodecRow(True, None),
+}
 
 _ctx = {}
 _ws = {}

@@ -40,7 +40,7 @@ from .. import config as _settings
 from ..collector import collector as _collector_mod
 from ..prof import Profiler
 from .patchpara.df_cache import AllGatherCache
-from .utils import ALLOW_DEPRECATED, COMPACT_COMPRESS_TYPE, CompactCache, CompactConfig
+from .utils import ALLOW_DEPRECATED, COMPACT_COMPRESS_TYPE, NATIVE_CODEC, CompactCache, CompactConfig
 
 T = COMPACT_COMPRESS_TYPE
 
@@ -156,32 +156,21 @@ def _native(compress_type: T) -> Tuple[int, int]:
             assert 1 <= rank <= 32, "1-bit with subspace-iteration scales: comp_rank must be 1..32 (the factor chain's limit)"
             from . import lowrank
             return lowrank.BINARY_RANK_ID, int(rank)
-        return int(codecs.Codec.BINARY), 0
-    if compress_type == T.INT2:
-        return int(codecs.Codec.INT2), 0
-    if compress_type == T.INT4:
-        return int(codecs.Codec.INT4), 0
-    if compress_type == T.INT8:
-        return int(codecs.Codec.INT8), 0
-    if compress_type == T.INT2_MINMAX:
-        return int(codecs.Codec.INT2_MINMAX), 0
-    if compress_type == T.MXFP4:
-        return int(codecs.Codec.MXFP4), 0
-    if compress_type == T.BINARY_BLOCK:
-        return int(codecs.Codec.BINARY_BLOCK), int(_settings.get("binary_block"))
-    if compress_type == T.INT2_BLOCK:
-        return int(codecs.Codec.INT2_BLOCK), int(_settings.get("int2_block"))
-    if compress_type == T.INT3_BLOCK:
-        return int(codecs.Codec.INT3_BLOCK), int(_settings.get("int3_block"))
-    if compress_type == T.MXINT8:
-        return int(codecs.Codec.MXINT8), 0
     if compress_type == T.SPARSE:
         assert _config.sparse_ratio is not None, "sparse_ratio must be provided for SPARSE compression"
         return int(codecs.Codec.TOPK), int(_config.sparse_ratio)
     if compress_type in (T.LOW_RANK, T.LOW_RANK_Q):
         from . import lowrank
         return lowrank.native_id(compress_type), int(_config.comp_rank)
-    raise ValueError(f"Invalid compress_type value: {compress_type}")
+    if compress_type not in NATIVE_CODEC:
+        raise ValueError(f"Invalid compress_type value: {compress_type}")
+    codec = NATIVE_CODEC[compress_type]
+    setting = codecs.CODEC_TABLE[codec].setting
+    return int(codec), int(_settings.get(setting)) if setting else 0
+
+
+# the compress types whose codec takes bf16 tensors, in codec id order
+_BF16_TYPES = tuple(t for t, c in sorted(NATIVE_CODEC.items(), key=lambda tc: tc[1]) if codecs.CODEC_TABLE[c].bf16)
 
 
 def _check_bf16(dtype, compress_type: T) -> None:
@@ -191,10 +180,11 @@ def _check_bf16(dtype, compress_type: T) -> None:
     cfg = _config
 
     def no(option: str):
-        raise NotImplementedError(f"torch.bfloat16 activations are not supported with {option}: bf16 runs with BINARY (comp_rank -1) / INT2 / BINARY_BLOCK / INT2_BLOCK / INT3_BLOCK / MXINT8 / "
+        names = " / ".join("BINARY (comp_rank -1)" if t == T.BINARY else t.name for t in _BF16_TYPES)
+        raise NotImplementedError(f"torch.bfloat16 activations are not supported with {option}: bf16 runs with {names} / "
                                   "WARMUP / IDENTITY, compress_residual 0 or 1, no simulation, no quantized cache - use fp16 activations "
                                   "for anything else")
-    if compress_type not in (T.BINARY, T.INT2, T.BINARY_BLOCK, T.INT2_BLOCK, T.INT3_BLOCK, T.MXINT8, T.WARMUP, T.IDENTITY):
+    if compress_type not in _BF16_TYPES + (T.WARMUP, T.IDENTITY):
         no(f"compress type {getattr(compress_type, 'name', compress_type)}")
     if compress_type == T.BINARY and cfg.comp_rank is not None and cfg.comp_rank != -1:
         no(f"BINARY with comp_rank {cfg.comp_rank} (rank-K scales)")

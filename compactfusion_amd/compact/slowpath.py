@@ -13,10 +13,10 @@ import torch
 
 from .. import codecs
 from .compress_topk import SPARSE_LAST_DIM_SIZE  # noqa: F401
-from .utils import COMPACT_COMPRESS_TYPE as T
+from .utils import COMPACT_COMPRESS_TYPE as T, NATIVE_CODEC
 
-_MAP = {T.BINARY: codecs.Codec.BINARY, T.INT2: codecs.Codec.INT2, T.INT4: codecs.Codec.INT4, T.INT8: codecs.Codec.INT8,
-        T.SPARSE: codecs.Codec.TOPK, T.INT2_MINMAX: codecs.Codec.INT2_MINMAX, T.MXFP4: codecs.Codec.MXFP4, T.MXINT8: codecs.Codec.MXINT8}
+# (a codec whose param is a host switch is no slowpath wire codec)
+_MAP = {t: c for t, c in NATIVE_CODEC.items() if codecs.CODEC_TABLE[c].setting is None}
 
 
 def _resolve(compress_type, rank, sparse_ratio):

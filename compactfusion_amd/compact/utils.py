@@ -15,6 +15,7 @@ from typing import Callable, Dict, Optional
 import torch
 import torch.distributed as dist
 
+from ..codecs import Codec
 from .patchpara.df_utils import PatchConfig
 
 ALLOW_DEPRECATED = os.environ.get("COMPACT_ALLOW_DEPRECATED", "0") == "1"
@@ -44,6 +45,22 @@ class COMPACT_COMPRESS_TYPE(Enum):
     INT2_BLOCK = "int2-block"       # extension (not in the reference enum)
     INT3_BLOCK = "int3-block"       # extension (not in the reference enum)
     MXINT8 = "mxint8"               # extension (not in the reference enum)
+
+
+# the compress types that ARE a streaming codec of libcfx.so (codecs.CODEC_TABLE has each one's row)
+NATIVE_CODEC = {
+    COMPACT_COMPRESS_TYPE.BINARY: Codec.BINARY,
+    COMPACT_COMPRESS_TYPE.INT2: Codec.INT2,
+    COMPACT_COMPRESS_TYPE.INT4: Codec.INT4,
+    COMPACT_COMPRESS_TYPE.INT8: Codec.INT8,
+    COMPACT_COMPRESS_TYPE.SPARSE: Codec.TOPK,
+    COMPACT_COMPRESS_TYPE.INT2_MINMAX: Codec.INT2_MINMAX,
+    COMPACT_COMPRESS_TYPE.MXFP4: Codec.MXFP4,
+    COMPACT_COMPRESS_TYPE.BINARY_BLOCK: Codec.BINARY_BLOCK,
+    COMPACT_COMPRESS_TYPE.INT2_BLOCK: Codec.INT2_BLOCK,
+    COMPACT_COMPRESS_TYPE.INT3_BLOCK: Codec.INT3_BLOCK,
+    COMPACT_COMPRESS_TYPE.MXINT8: Codec.MXINT8,
+}
 
 
 class CompactConfig:

@@ -404,8 +404,7 @@ class LayerOp:
         # element type of the layer: the states' (fp16, or bf16 with the 1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit codecs and MXINT8 - include/cfx.h, "bf16 activations"); the
         # activations of every run must have it.  `cabi` is the C-ABI's codec argument: the id, with CFX_ELEM_BF16 for bf16
         self.dtype = codecs.elem_dtype(*self.own, *[t for _, ks, vs in self.peers for t in (ks, vs)])
-        if self.dtype == torch.bfloat16 and self.cid not in (int(codecs.Codec.BINARY), int(codecs.Codec.INT2), int(codecs.Codec.BINARY_BLOCK), int(codecs.Codec.INT2_BLOCK),
-                                                              int(codecs.Codec.INT3_BLOCK), int(codecs.Codec.MXINT8)):
+        if self.dtype == torch.bfloat16 and not (self.cid in codecs.CODEC_TABLE and codecs.CODEC_TABLE[self.cid].bf16):
             raise NotImplementedError(f"torch.bfloat16 activations are not supported with codec id {self.cid} in the layer exchange op "
                                       "(bf16 runs with the 1-bit, 2-bit and block-scaled 1-bit / 2-bit / 3-bit codecs and MXINT8)")
         self.cabi = self.cid if self.lowrank else codecs.codec_arg(self.cid, self.dtype)
@@ -894,4 +893,4 @@ class LayerOp:
 def usable(cid: int, world: int, is_cuda: bool, ef: bool = True) -> bool:
     """Can the layer's exchange run as a LayerOp: a native streaming codec - or the low-rank family with error feedback -, W ranks whose
     2 (W - 1) peer tensors + own K,V fit one batch."""
-    return is_cuda and (cid in (1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16) or (cid in (101, 102) and ef)) and 2 * (world - 1) + 2 <= MAX_ITEMS
+    return is_cuda and (cid in codecs.CODEC_TABLE or (cid in (101, 102) and ef)) and 2 * (world - 1) + 2 <= MAX_ITEMS

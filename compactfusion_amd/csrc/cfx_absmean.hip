@@ -1859,16 +1859,18 @@ int cfx_i_absmean_compress(CompressCall& cc) {
     return check_launch(ctx, "compress launch");
 }
 
-int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, bool bf16, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val) {
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, batch);
-    if (codec == CFX_CODEC_BINARY) {
-        if (stream_cu_count(ctx, stream) < 128) {
+int cfx_i_absmean_decompress(const DecompressCall& dc) {
+    cfx_ctx* ctx = dc.ctx;
+    const int N = dc.N, C = dc.C, R = dc.R;
+    hipStream_t s = (hipStream_t)dc.stream;
+    const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, dc.batch);
+    if (dc.codec == CFX_CODEC_BINARY) {
+        if (stream_cu_count(ctx, dc.stream) < 128) {
             // a CU-masked lane is bound by the bytes each CU keeps in flight: 4 rows per wave instead of 2
             const int R4 = WAVES * 4;
-            LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<4, EL>), dim3(grid.x, (N + R4 - 1) / R4, batch), dim3(NTHR), 0, s, b, N, C, R4, pre, pre_val);
-        } else LAUNCH_EL(bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<UNROLL, EL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
-    } else LAUNCH_EL(bf16, ctx, KID_INT2_DEQUANT, s, (k_int2_dequant<EL>), grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+            LAUNCH_EL(dc.bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<4, EL>), dim3(grid.x, (N + R4 - 1) / R4, dc.batch), dim3(NTHR), 0, s, dc.b, N, C, R4, dc.pre, dc.pre_val);
+        } else LAUNCH_EL(dc.bf16, ctx, KID_BINARY_DEQUANT, s, (k_binary_dequant<UNROLL, EL>), grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
+    } else LAUNCH_EL(dc.bf16, ctx, KID_INT2_DEQUANT, s, (k_int2_dequant<EL>), grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
     return check_launch(ctx, "decompress launch");
 }
 

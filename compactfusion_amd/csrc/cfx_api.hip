@@ -189,26 +189,60 @@ __global__ __launch_bounds__(256) void k_attn_merge_ex(float* __restrict__ out, 
 // ---------------------------------------------------------------------------------------------------
 // host side: C-ABI
 // ---------------------------------------------------------------------------------------------------
-static bool shape_ok(int codec, int N, int C, int param) {
-    bool bf16;
-    codec = codec_id(codec, &bf16);                 // (the sizes and shape rules of a bf16 call are the fp16 codec's)
-    if (N <= 0 || C <= 0 || (C % 8) != 0) return false;
-    switch (codec) {
-        case CFX_CODEC_BINARY: return ((size_t)N * (C / 8)) % 2 == 0;
-        case CFX_CODEC_INT2: return true;
-        case CFX_CODEC_INT4: return N % 2 == 0;
-        case CFX_CODEC_INT8: return true;
-        case CFX_CODEC_INT2_MINMAX: return N % 4 == 0;
-        case CFX_CODEC_MXFP4:
-        case CFX_CODEC_MXINT8: return C % 64 == 0 && param == 0;
-        case CFX_CODEC_BINARY_BLOCK:
-        case CFX_CODEC_INT2_BLOCK:
-        case CFX_CODEC_INT3_BLOCK: return (param == 32 || param == 64 || param == 128) && C % (param > 64 ? param : 64) == 0;
-        case CFX_CODEC_TOPK:
-            return ((size_t)N * C) % 1024 == 0 && (param == 1 || param == 2 || param == 4 || param == 8 || param == 16);
-        default: return false;
-    }
+// The codec table: one row per streaming codec (CfxCodec, cfx_internal.h).  Which ids exist, what each accepts, its shape rule and sizes,
+// and who launches it are said HERE and nowhere else.
+static bool any_shape(int, int, int) { return true; }
+static bool mx_shape(int, int C, int param) { return C % 64 == 0 && param == 0; }                          // 32-element blocks, a wave step of 64
+static bool block_shape(int, int C, int B) { return (B == 32 || B == 64 || B == 128) && C % (B > 64 ? B : 64) == 0; }
+static size_t no_ws(int, int) { return 0; }
+// worst case R = 16
+static size_t absmean_ws(int N, int C) {
+    const size_t CB = (C + TILE_C - 1) / TILE_C, P = (N + 15) / 16;
+    return (size_t)N * CB + P * C + ((size_t)N * CB + P * C + 1) / 2;      // + the 32-bit partials of the fused path
 }
+static size_t minmax_ws(int N, int C) { return ((size_t)((N + 15) / 16) * C + 1) / 2; }
+#define ROW_FN(name) cfx_i_##name##_compress, cfx_i_##name##_decompress
+static const CfxCodec codec_table[] = {
+    // id, name, bf16, second_order, ride, tiled, shape, packet_bytes, ws_words, compress, decompress
+    {CFX_CODEC_BINARY, "binary", true, true, true, true, [](int N, int C, int) { return ((size_t)N * (C / 8)) % 2 == 0; },
+     [](size_t n, size_t c, size_t) { return n * c / 8 + 2 * (n + c); }, absmean_ws, ROW_FN(absmean)},
+    {CFX_CODEC_INT2, "int2", true, true, false, true, any_shape,
+     [](size_t n, size_t c, size_t) { return n * c / 4 + 2 * (n + c); }, absmean_ws, ROW_FN(absmean)},
+    {CFX_CODEC_INT4, "int4", false, false, false, true, [](int N, int, int) { return N % 2 == 0; },
+     [](size_t n, size_t c, size_t) { return n * c / 2 + 4 * c; }, minmax_ws, ROW_FN(minmax)},
+    {CFX_CODEC_INT8, "int8", false, false, false, true, any_shape,
+     [](size_t n, size_t c, size_t) { return n * c + 4 * c; }, minmax_ws, ROW_FN(minmax)},
+    {CFX_CODEC_TOPK, "topk", false, false, false, false,
+     [](int N, int C, int m) { return ((size_t)N * C) % 1024 == 0 && (m == 1 || m == 2 || m == 4 || m == 8 || m == 16); },
+     [](size_t n, size_t c, size_t m) { return 2 * (n * c / m) + n * c / (2 * m); }, no_ws, ROW_FN(topk)},
+    {CFX_CODEC_INT2_MINMAX, "int2-minmax", false, false, false, true, [](int N, int, int) { return N % 4 == 0; },
+     [](size_t n, size_t c, size_t) { return n * c / 4 + 4 * c; }, minmax_ws, ROW_FN(minmax)},
+    {CFX_CODEC_MXFP4, "mxfp4", false, false, false, false, mx_shape,
+     [](size_t n, size_t c, size_t) { return n * c / 2 + n * c / 32; }, no_ws, ROW_FN(mx)},
+    {CFX_CODEC_BINARY_BLOCK, "binary-block", true, false, false, false, block_shape,
+     [](size_t n, size_t c, size_t B) { return n * c / 8 + 2 * (n * c / B); }, no_ws, ROW_FN(bb)},
+    {CFX_CODEC_INT2_BLOCK, "int2-block", true, false, false, false, block_shape,
+     [](size_t n, size_t c, size_t B) { return n * c / 4 + 2 * (n * c / B); }, no_ws, ROW_FN(i2b)},
+    {CFX_CODEC_INT3_BLOCK, "int3-block", true, false, false, false, block_shape,
+     [](size_t n, size_t c, size_t B) { return n * c / 4 + n * c / 8 + 2 * (n * c / B); }, no_ws, ROW_FN(i3b)},
+    {CFX_CODEC_MXINT8, "mxint8", true, false, false, false, mx_shape,
+     [](size_t n, size_t c, size_t) { return n * c + n * c / 32; }, no_ws, ROW_FN(mxi8)},
+};
+#undef ROW_FN
+
+const CfxCodec* cfx_i_codec(int id) {
+    for (const CfxCodec& k : codec_table)
+        if (k.id == id) return &k;
+    return nullptr;
+}
+
+// the row of a `codec` argument whose shape and param the codec accepts, else NULL (the sizes and shape rules of a bf16 call are the fp16 codec's)
+static const CfxCodec* codec_for(int codec, int N, int C, int param) {
+    bool bf16;
+    const CfxCodec* k = cfx_i_codec(codec_id(codec, &bf16));
+    return (k && N > 0 && C > 0 && (C % 8) == 0 && k->shape(N, C, param)) ? k : nullptr;
+}
+static bool shape_ok(int codec, int N, int C, int param) { return codec_for(codec, N, C, param) != nullptr; }
 
 int cfx_i_auto_rows(const cfx_ctx* ctx, int N, int C, int batch, bool stats) {
     if (ctx && ctx->rows_per_tile > 0) {
@@ -443,35 +477,14 @@ int cfx_set_rows_per_tile(cfx_ctx* ctx, int rows) {
 }
 
 size_t cfx_packet_bytes(int codec, int N, int C, int param) {
-    if (!shape_ok(codec, N, C, param)) return 0;
-    const size_t n = N, c = C;
-    switch (codec & 0xff) {
-        case CFX_CODEC_BINARY: return n * c / 8 + 2 * (n + c);
-        case CFX_CODEC_INT2: return n * c / 4 + 2 * (n + c);
-        case CFX_CODEC_INT4: return n * c / 2 + 4 * c;
-        case CFX_CODEC_INT8: return n * c + 4 * c;
-        case CFX_CODEC_INT2_MINMAX: return n * c / 4 + 4 * c;
-        case CFX_CODEC_MXFP4: return n * c / 2 + n * c / 32;
-        case CFX_CODEC_BINARY_BLOCK: return n * c / 8 + 2 * (n * c / param);
-        case CFX_CODEC_INT2_BLOCK: return n * c / 4 + 2 * (n * c / param);
-        case CFX_CODEC_INT3_BLOCK: return n * c / 4 + n * c / 8 + 2 * (n * c / param);
-        case CFX_CODEC_MXINT8: return n * c + n * c / 32;
-        case CFX_CODEC_TOPK: return 2 * (n * c / param) + n * c / (2 * param);
-    }
-    return 0;
+    const CfxCodec* k = codec_for(codec, N, C, param);
+    return k ? k->packet_bytes((size_t)N, (size_t)C, (size_t)param) : 0;
 }
 
-// per-tensor workspace in u64 words (worst case R = 16)
+// per-tensor workspace in u64 words
 static size_t ws_words(int codec, int N, int C) {
-    const size_t CB = (C + TILE_C - 1) / TILE_C, P = (N + 15) / 16;
-    switch (codec & 0xff) {
-        case CFX_CODEC_BINARY:
-        case CFX_CODEC_INT2: return (size_t)N * CB + P * C + ((size_t)N * CB + P * C + 1) / 2;      // + the 32-bit partials of the fused path
-        case CFX_CODEC_INT4:
-        case CFX_CODEC_INT8:
-        case CFX_CODEC_INT2_MINMAX: return (P * C + 1) / 2;
-        default: return 0;
-    }
+    const CfxCodec* k = cfx_i_codec(codec & 0xff);
+    return k ? k->ws_words(N, C) : 0;
 }
 
 size_t cfx_workspace_bytes(int codec, int N, int C, int param, int batch) {
@@ -507,27 +520,17 @@ int cfx_i_decompress_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int para
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "decompress: null ctx/items");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "decompress: batch out of range");
     if (!shape_ok(codec, N, C, param)) return fail(ctx, codec_known(codec) ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
-    BatchD b;
-    memset(&b, 0, sizeof(b));
+    DecompressCall dc;
+    memset(&dc.b, 0, sizeof(dc.b));
     for (int i = 0; i < batch; ++i) {
         if (!items[i].packet || !items[i].recon) return fail(ctx, CFX_ERR_NULL, "decompress: null packet/recon");
         if (!AL16(items[i].packet) || !AL16(items[i].recon) || !AL16(items[i].base)) return fail(ctx, CFX_ERR_ALIGN, "decompress: pointers must be 16-byte aligned");
-        b.it[i] = items[i];
+        dc.b.it[i] = items[i];
     }
-    const int R = auto_rows(ctx, N, C, batch, false);
-    switch (codec) {
-        case CFX_CODEC_BINARY:
-        case CFX_CODEC_INT2: return cfx_i_absmean_decompress(ctx, codec, bf16, N, C, batch, b, R, stream, pre, pre_val);
-        case CFX_CODEC_INT4:
-        case CFX_CODEC_INT8:
-        case CFX_CODEC_INT2_MINMAX: return cfx_i_minmax_decompress(ctx, codec, N, C, batch, b, R, stream, pre, pre_val);
-        case CFX_CODEC_MXFP4: return cfx_i_mx_decompress(ctx, N, C, batch, b, stream, pre, pre_val);
-        case CFX_CODEC_BINARY_BLOCK: return cfx_i_bb_decompress(ctx, bf16, N, C, param, batch, b, stream, pre, pre_val);
-        case CFX_CODEC_INT2_BLOCK: return cfx_i_i2b_decompress(ctx, bf16, N, C, param, batch, b, stream, pre, pre_val);
-        case CFX_CODEC_INT3_BLOCK: return cfx_i_i3b_decompress(ctx, bf16, N, C, param, batch, b, stream, pre, pre_val);
-        case CFX_CODEC_MXINT8: return cfx_i_mxi8_decompress(ctx, bf16, N, C, batch, b, stream, pre, pre_val);
-        default: return cfx_i_topk_decompress(ctx, N, C, param, batch, b, stream, pre, pre_val);
-    }
+    dc.ctx = ctx; dc.codec = codec; dc.bf16 = bf16; dc.N = N; dc.C = C; dc.param = param; dc.batch = batch;
+    dc.R = auto_rows(ctx, N, C, batch, false);
+    dc.stream = stream; dc.pre = pre; dc.pre_val = pre_val;
+    return cfx_i_codec(codec)->decompress(dc);
 }
 
 int cfx_decompress_batch(cfx_ctx* ctx, int codec, int N, int C, int param, int batch, const cfx_decomp_item* items, void* stream) {
@@ -542,7 +545,7 @@ int cfx_i_decompress2_checked(cfx_ctx* ctx, int codec_arg, int N, int C, int par
     if (!ctx || !items || !second) return fail(ctx, CFX_ERR_NULL, "decompress: null ctx/items/second");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "decompress: batch out of range");
     if (!shape_ok(codec, N, C, param)) return fail(ctx, codec_known(codec) ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "decompress: bad codec/shape");
-    if ((codec != CFX_CODEC_BINARY && codec != CFX_CODEC_INT2) || bf16)
+    if (!cfx_i_codec(codec)->second_order || bf16)
         return fail(ctx, CFX_ERR_CODEC, "decompress: second-order states need the 1-bit or 2-bit codec, fp16");
     BatchD2 b;
     memset(&b, 0, sizeof(b));
@@ -629,11 +632,12 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     if (!ctx || !items) return fail(ctx, CFX_ERR_NULL, "compress: null ctx/items");
     if (n_gated < 0 || n_gated > CFX_MAX_BATCH || (n_gated && !gated)) return fail(ctx, CFX_ERR_BATCH, "compress: gated batch out of range");
     if (batch < 1 || batch > CFX_MAX_BATCH) return fail(ctx, CFX_ERR_BATCH, "compress: batch out of range");
-    if (!shape_ok(codec, N, C, param)) return fail(ctx, codec_known(codec) ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "compress: bad codec/shape");
+    const CfxCodec* k = cfx_i_codec(codec);
+    if (!shape_ok(codec, N, C, param)) return fail(ctx, k ? CFX_ERR_SHAPE : CFX_ERR_CODEC, "compress: bad codec/shape");
     if (n_ride < 0 || n_ride > CFX_MAX_BATCH || (n_ride && !ride)) return fail(ctx, CFX_ERR_BATCH, "compress: ride-along batch out of range");
-    if (n_ride && codec != CFX_CODEC_BINARY) return fail(ctx, CFX_ERR_CODEC, "compress: ride-along reconstruction items need the 1-bit codec");
+    if (n_ride && !k->ride) return fail(ctx, CFX_ERR_CODEC, "compress: ride-along reconstruction items need the 1-bit codec");
     // second-order states (include/cfx.h, "Second-order residual"): the 1-bit and 2-bit codecs, fp16, error feedback on, no layer form
-    if (second && ((codec != CFX_CODEC_BINARY && codec != CFX_CODEC_INT2) || bf16 || (flags & CFX_FLAG_NO_EF) || n_ride || n_gated || xg))
+    if (second && (!k->second_order || bf16 || (flags & CFX_FLAG_NO_EF) || n_ride || n_gated || xg))
         return fail(ctx, CFX_ERR_CODEC, "compress: second-order states need the 1-bit or 2-bit codec, fp16, no CFX_FLAG_NO_EF, no ride-along / gated items");
     const bool upd = flags & CFX_FLAG_UPDATE_CACHE;
     BatchC b;
@@ -689,14 +693,9 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     cc.ws = ws; cc.wstride = wstride; cc.CB = CB; cc.upd = upd; cc.capturing = capturing; cc.bf16 = bf16;
     cc.fused = false; cc.tick = nullptr; cc.slot = 0; cc.stream_cus = 0; cc.R = cc.P = 0;
     cc.second = second; cc.decay = decay;
-    if (codec == CFX_CODEC_TOPK) return cfx_i_topk_compress(cc);
-    if (codec == CFX_CODEC_MXFP4) return cfx_i_mx_compress(cc);
-    if (codec == CFX_CODEC_BINARY_BLOCK) return cfx_i_bb_compress(cc);
-    if (codec == CFX_CODEC_INT2_BLOCK) return cfx_i_i2b_compress(cc);
-    if (codec == CFX_CODEC_INT3_BLOCK) return cfx_i_i3b_compress(cc);
-    if (codec == CFX_CODEC_MXINT8) return cfx_i_mxi8_compress(cc);
+    if (!k->tiled) return k->compress(cc);
 
-    // statistics + finalize: ONE launch with the in-launch finalize (default), or the two-kernel sequence
+    // the abs-mean and min/max families: statistics + finalize: ONE launch with the in-launch finalize (default), or the two-kernel sequence
     const bool fused = ctx->fused && CB <= TICK_MAX_CB;
     // Ticket / gate blocks are handed out round-robin from a ring PER STREAM (launches of one stream are in order, so a ring slot is
     // never shared by two launches in flight; one ring for every stream would let a stalled stream's launch meet a slot that another
@@ -714,7 +713,7 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     const int R = fused ? fused_rows(ctx, N, C, batch, stream_cus) : auto_rows(ctx, N, C, batch, true);
     const int P = (N + R - 1) / R;
     cc.fused = fused; cc.tick = tick; cc.slot = slot; cc.stream_cus = stream_cus; cc.R = R; cc.P = P;
-    return (codec == CFX_CODEC_BINARY || codec == CFX_CODEC_INT2) ? cfx_i_absmean_compress(cc) : cfx_i_minmax_compress(cc);
+    return k->compress(cc);
 }
 
 int cfx_compress_batch_ex(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,

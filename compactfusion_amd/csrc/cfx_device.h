@@ -1,4 +1,4 @@
-// Device code shared by the codec families of libcfx.so (cfx_absmean.hip, cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip, cfx_i2block.hip, cfx_i3block.hip, cfx_mxint8.hip, cfx_api.hip): element types, loads /
+// Device code shared by the codec families of libcfx.so (the family files of compactfusion_amd/build.py SRC, and cfx_api.hip): element types, loads /
 // stores, the tagged-word arenas, tile coordinates, the ticket / gate geometry and the in-launch waits, the peer-to-peer exchange a layer
 // launch runs inside itself.  (Round 6: cfx_kernels.hip was one 4 130-line translation unit; it is now this header + one file per family
 // + the C-ABI.)

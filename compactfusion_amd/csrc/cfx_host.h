@@ -1,6 +1,6 @@
-// Host-side internals shared by the translation units of libcfx.so's streaming codecs (cfx_api.hip: context, C-ABI, dispatch; cfx_absmean.hip,
-// cfx_minmax.hip, cfx_topk.hip, cfx_mx.hip, cfx_bblock.hip, cfx_i2block.hip, cfx_i3block.hip, cfx_mxint8.hip: each family's kernels AND the code that launches them; cfx_local.h: the launch
-// skeleton the last three - the block-local codecs - share).  Not part of the ABI.
+// Host-side internals shared by the translation units of libcfx.so's streaming codecs (compactfusion_amd/build.py SRC: cfx_api.hip - context,
+// C-ABI, the codec table and its dispatch - and one file per codec family, with the family's kernels AND the code that launches them).
+// Not part of the ABI.
 #ifndef CFX_HOST_H
 #define CFX_HOST_H
 #include "cfx_device.h"
@@ -29,25 +29,26 @@ struct CompressCall {
     const cfx_second_item* second;   // != NULL: second-order states of the items (cfx_compress_batch_res2; 1-bit / 2-bit, fp16) and their decay
     float decay;
 };
+// One reconstruction call after validation (cfx_api.hip's cfx_i_decompress_checked).  `pre` / `pre_val`: an optional flag word the launch publishes
+struct DecompressCall {
+    cfx_ctx* ctx;
+    int codec, N, C, param, batch;
+    bool bf16;
+    BatchD b;
+    int R;                           // rows of a tile (the abs-mean and min/max families)
+    void* stream;
+    unsigned* pre;
+    unsigned pre_val;
+};
 extern "C" {
-CFX_HIDDEN int cfx_i_topk_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_mx_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_bb_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_i2b_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_i3b_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_mxi8_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_absmean_compress(CompressCall& cc);
-CFX_HIDDEN int cfx_i_minmax_compress(CompressCall& cc);
-// reconstruction launches of a validated batch (decompress_impl's dispatch); `pre` / `pre_val`: an optional flag word the kernel waits for
-CFX_HIDDEN int cfx_i_absmean_decompress(cfx_ctx* ctx, int codec, bool bf16, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
+// a family's two launchers, as the rows of cfx_api.hip's codec_table name them
+#define CFX_FAMILY(name) \
+    CFX_HIDDEN int cfx_i_##name##_compress(CompressCall& cc); \
+    CFX_HIDDEN int cfx_i_##name##_decompress(const DecompressCall& dc);
+CFX_FAMILY(absmean) CFX_FAMILY(minmax) CFX_FAMILY(topk) CFX_FAMILY(mx) CFX_FAMILY(bb) CFX_FAMILY(i2b) CFX_FAMILY(i3b) CFX_FAMILY(mxi8)
+#undef CFX_FAMILY
+// second order: the abs-mean family's reconstruction with a batch type of its own
 CFX_HIDDEN int cfx_i_absmean_decompress2(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD2& b, int R, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_minmax_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_topk_decompress(cfx_ctx* ctx, int N, int C, int param, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_mx_decompress(cfx_ctx* ctx, int N, int C, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_bb_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_i2b_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_i3b_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
-CFX_HIDDEN int cfx_i_mxi8_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val);
 // cfx_api.hip
 CFX_HIDDEN int cfx_i_auto_rows(const cfx_ctx* ctx, int N, int C, int batch, bool stats);
 CFX_HIDDEN int cfx_i_fused_rows(const cfx_ctx* ctx, int N, int C, int batch, int cus);

@@ -128,22 +128,4 @@ __global__ __launch_bounds__(256) void k_i3b_decompress(BatchD batch, size_t E, 
 // ---------------------------------------------------------------------------------------------------
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
-int cfx_i_i3b_compress(CompressCall& cc) {
-    cfx_ctx* ctx = cc.ctx;
-    hipStream_t s = (hipStream_t)cc.stream;
-    LocalLayerArgs a;
-    const int lg = cfx_i_local_layer(cc, a);
-    if (lg < 0) return lg;
-    if (lg) {
-        BB_LAUNCH(cc.bf16, cc.param, KID_ABSMEAN_COMPRESS_GATED, k_i3b_layer, dim3((unsigned)lg), cc.b, cc.gd, a);
-        return check_launch(ctx, "int3-block layer launch");
-    }
-    BB_LAUNCH(cc.bf16, cc.param, KID_TOPK_COMPRESS, k_i3b_compress, cfx_i_local_grid(cc.N, cc.C, cc.batch), cc.b, (size_t)cc.N * cc.C, cc.flags);
-    return cfx_i_local_tail(cc, "int3-block compress launch");
-}
-
-int cfx_i_i3b_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int B, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val) {
-    hipStream_t s = (hipStream_t)stream;
-    BB_LAUNCH(bf16, B, KID_TOPK_DECOMPRESS, k_i3b_decompress, cfx_i_local_grid(N, C, batch), b, (size_t)N * C, pre, pre_val);
-    return check_launch(ctx, "decompress launch");
-}
+LOCAL_FAMILY_HOST(i3b, "int3-block", BB_LAUNCH)

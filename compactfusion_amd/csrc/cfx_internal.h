@@ -170,23 +170,40 @@ static inline int check_launch(cfx_ctx* ctx, const char* what) {
 
 #define AL16(p) ((((uintptr_t)(p)) & 15) == 0)
 
+// What the library knows about ONE streaming codec (include/cfx.h enum cfx_codec): a row of cfx_api.hip's codec_table, the only place that
+// says which codecs exist, what each accepts and who launches it.  Everything else asks cfx_i_codec.
+#define CFX_HIDDEN __attribute__((visibility("hidden")))
+struct CompressCall;                 // cfx_host.h
+struct DecompressCall;
+struct CfxCodec {
+    int id;
+    const char* name;
+    bool bf16;                       // takes CFX_ELEM_BF16 on the codec argument
+    bool second_order;               // takes second-order states (fp16 calls only)
+    bool ride;                       // takes ride-along reconstruction items
+    bool tiled;                      // compress_impl works out the tile geometry (CompressCall fused .. P) before `compress`
+    bool (*shape)(int N, int C, int param);                         // the codec's own rule, on top of N > 0, C > 0, C % 8 == 0
+    size_t (*packet_bytes)(size_t n, size_t c, size_t param);       // of a shape that passed
+    size_t (*ws_words)(int N, int C);                               // per-tensor workspace in u64 words
+    int (*compress)(CompressCall& cc);
+    int (*decompress)(const DecompressCall& dc);
+};
+CFX_HIDDEN const CfxCodec* cfx_i_codec(int id);      // the row of codec `id`, NULL: no such codec
+
 // A `codec` argument of the ABI -> the codec id and the element type of the call's tensors (CFX_ELEM_BF16, include/cfx.h).  0 - no codec -
 // for any other high bit and for the bf16 bit on a codec that has no bf16 form.
 static inline int codec_id(int codec_arg, bool* bf16) {
     const int id = codec_arg & 0xff;
     *bf16 = (codec_arg & CFX_ELEM_BF16) != 0;
     if (codec_arg < 0 || (codec_arg & ~(0xff | CFX_ELEM_BF16))) return 0;
-    if (*bf16 && id != CFX_CODEC_BINARY && id != CFX_CODEC_INT2 && id != CFX_CODEC_BINARY_BLOCK && id != CFX_CODEC_INT2_BLOCK && id != CFX_CODEC_INT3_BLOCK &&
-        id != CFX_CODEC_MXINT8)
-        return 0;
+    if (*bf16) {
+        const CfxCodec* k = cfx_i_codec(id);
+        if (!k || !k->bf16) return 0;
+    }
     return id;
 }
 
-// the streaming codecs' ids (include/cfx.h enum cfx_codec; 7, 9, 11, 13 and 15 are not)
-static inline bool codec_known(int id) {
-    return (id >= CFX_CODEC_BINARY && id <= CFX_CODEC_INT2_MINMAX) || id == CFX_CODEC_MXFP4 || id == CFX_CODEC_BINARY_BLOCK || id == CFX_CODEC_INT2_BLOCK ||
-           id == CFX_CODEC_INT3_BLOCK || id == CFX_CODEC_MXINT8;
-}
+static inline bool codec_known(int id) { return cfx_i_codec(id) != nullptr; }
 
 // ---------------------------------------------------------------------------------------------------
 // Plan / communicator internals, shared by cfx_absmean.hip (the fused pipeline launch) and cfx_plan.hip (everything else)
@@ -292,7 +309,6 @@ struct PipeSched {
 };
 
 // cfx_api.hip (the fused pipeline launch: cfx_absmean.hip), for cfx_plan.hip (hidden: not part of the ABI)
-#define CFX_HIDDEN __attribute__((visibility("hidden")))
 CFX_HIDDEN bool cfx_i_shape_ok(int codec, int N, int C, int param);
 CFX_HIDDEN size_t cfx_i_ws_words(int codec, int N, int C);
 // a zeroed block of CFX_MAX_BATCH * 64 u32 ticket words for ONE launch on `stream`; whoever draws a word's final value resets it to 0

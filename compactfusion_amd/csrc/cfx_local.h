@@ -1,4 +1,4 @@
-// The launch skeleton of libcfx.so's BLOCK-LOCAL wire codecs - top-k (cfx_topk.hip), MXFP4 (cfx_mx.hip), BINARY_BLOCK (cfx_bblock.hip), INT2_BLOCK (cfx_i2block.hip), INT3_BLOCK (cfx_i3block.hip), MXINT8 (cfx_mxint8.hip): a
+// The launch skeleton of libcfx.so's BLOCK-LOCAL wire codecs (the family files of compactfusion_amd/build.py SRC that include this header): a
 // block's packet words are a function of the block alone, so nothing global is waited for.  Held once here: the bodies of the stand-alone
 // compress / decompress kernels and of the one-launch layer (LOCAL_LAYER), and the host code of the layer form (decision, gate bookkeeping,
 // hand-over to an exchange-layer op).  A family file keeps its codec - a policy type P - and its __global__ kernels, one-line wrappers of these bodies:
@@ -176,4 +176,29 @@ inline int cfx_i_local_tail(CompressCall& cc, const char* what) {
     if (rc != CFX_OK || cc.xg || !cc.n_gated) return rc;
     return cfx_i_decompress_impl(cc.ctx, cc.codec | (cc.bf16 ? CFX_ELEM_BF16 : 0), cc.N, cc.C, cc.param, cc.n_gated, cc.gated, cc.stream, nullptr, 0u);
 }
+
+// A family's two launchers (cfx_host.h CFX_FAMILY; the last line of a family file), for its kernels k_<name>_compress / _layer / _decompress.
+// `label`: the family's name in check_launch's messages.  PICK(bf16, param, kid, kern, grid, ...): launches the instantiation of the template
+// `kern` that the call's element type and param select, with the caller's `ctx` and stream `s`; a family ignores what it has no template
+// argument for.
+#define LOCAL_FAMILY_HOST(name, label, PICK) \
+    int cfx_i_##name##_compress(CompressCall& cc) { \
+        cfx_ctx* ctx = cc.ctx; \
+        hipStream_t s = (hipStream_t)cc.stream; \
+        LocalLayerArgs a; \
+        const int lg = cfx_i_local_layer(cc, a); \
+        if (lg < 0) return lg; \
+        if (lg) { \
+            PICK(cc.bf16, cc.param, KID_ABSMEAN_COMPRESS_GATED, k_##name##_layer, dim3((unsigned)lg), cc.b, cc.gd, a); \
+            return check_launch(ctx, label " layer launch"); \
+        } \
+        PICK(cc.bf16, cc.param, KID_TOPK_COMPRESS, k_##name##_compress, cfx_i_local_grid(cc.N, cc.C, cc.batch), cc.b, (size_t)cc.N * cc.C, cc.flags); \
+        return cfx_i_local_tail(cc, label " compress launch"); \
+    } \
+    int cfx_i_##name##_decompress(const DecompressCall& dc) { \
+        cfx_ctx* ctx = dc.ctx; \
+        hipStream_t s = (hipStream_t)dc.stream; \
+        PICK(dc.bf16, dc.param, KID_TOPK_DECOMPRESS, k_##name##_decompress, cfx_i_local_grid(dc.N, dc.C, dc.batch), dc.b, (size_t)dc.N * dc.C, dc.pre, dc.pre_val); \
+        return check_launch(ctx, "decompress launch"); \
+    }
 #endif

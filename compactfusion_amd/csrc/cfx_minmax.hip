@@ -1224,12 +1224,14 @@ int cfx_i_minmax_compress(CompressCall& cc) {
     return check_launch(ctx, "compress launch");
 }
 
-int cfx_i_minmax_decompress(cfx_ctx* ctx, int codec, int N, int C, int batch, const BatchD& b, int R, void* stream, unsigned* pre, unsigned pre_val) {
-    hipStream_t s = (hipStream_t)stream;
-    if (codec == CFX_CODEC_INT2_MINMAX) R = (R + 3) & ~3;   // (row quads: see cfx_i_minmax_compress)
-    const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, batch);
-    if (codec == CFX_CODEC_INT4) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int4_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
-    else if (codec == CFX_CODEC_INT2_MINMAX) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int2mm_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
-    else LAUNCH(ctx, KID_INT8_DEQUANT, s, k_int8_dequant, grid, dim3(NTHR), 0, s, b, N, C, R, pre, pre_val);
+int cfx_i_minmax_decompress(const DecompressCall& dc) {
+    cfx_ctx* ctx = dc.ctx;
+    const int codec = dc.codec, N = dc.N, C = dc.C;
+    hipStream_t s = (hipStream_t)dc.stream;
+    const int R = codec == CFX_CODEC_INT2_MINMAX ? (dc.R + 3) & ~3 : dc.R;   // (row quads: see cfx_i_minmax_compress)
+    const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, dc.batch);
+    if (codec == CFX_CODEC_INT4) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int4_dequant, grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
+    else if (codec == CFX_CODEC_INT2_MINMAX) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int2mm_dequant, grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
+    else LAUNCH(ctx, KID_INT8_DEQUANT, s, k_int8_dequant, grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
     return check_launch(ctx, "decompress launch");
 }

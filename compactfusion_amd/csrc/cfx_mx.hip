@@ -148,22 +148,6 @@ __global__ __launch_bounds__(256) void k_mx_decompress(BatchD batch, size_t E, u
 // ---------------------------------------------------------------------------------------------------
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
-int cfx_i_mx_compress(CompressCall& cc) {
-    cfx_ctx* ctx = cc.ctx;
-    hipStream_t s = (hipStream_t)cc.stream;
-    LocalLayerArgs a;
-    const int lg = cfx_i_local_layer(cc, a);
-    if (lg < 0) return lg;
-    if (lg) {
-        LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, k_mx_layer, dim3((unsigned)lg), dim3(256), 0, s, cc.b, cc.gd, a);
-        return check_launch(ctx, "mxfp4 layer launch");
-    }
-    LAUNCH(ctx, KID_TOPK_COMPRESS, s, k_mx_compress, cfx_i_local_grid(cc.N, cc.C, cc.batch), dim3(256), 0, s, cc.b, (size_t)cc.N * cc.C, cc.flags);
-    return cfx_i_local_tail(cc, "mxfp4 compress launch");
-}
-
-int cfx_i_mx_decompress(cfx_ctx* ctx, int N, int C, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val) {
-    hipStream_t s = (hipStream_t)stream;
-    LAUNCH(ctx, KID_TOPK_DECOMPRESS, s, k_mx_decompress, cfx_i_local_grid(N, C, batch), dim3(256), 0, s, b, (size_t)N * C, pre, pre_val);
-    return check_launch(ctx, "decompress launch");
-}
+// the one instantiation of a kernel: cfx_internal.h's LAUNCH with the caller's `ctx` and stream `s`
+#define MX_LAUNCH(bf16, param, kid, kern, grid, ...) LAUNCH(ctx, kid, s, kern, grid, dim3(256), 0, s, __VA_ARGS__)
+LOCAL_FAMILY_HOST(mx, "mxfp4", MX_LAUNCH)

@@ -144,28 +144,10 @@ __global__ __launch_bounds__(256) void k_mxi8_decompress(BatchD batch, size_t E,
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
 // one of the two instantiations of a kernel template: the element type; cfx_host.h's LAUNCH with the caller's `ctx` and stream `s`
-#define MXI8_LAUNCH(bf16, kid, kern, grid, ...) \
+#define MXI8_LAUNCH(bf16, param, kid, kern, grid, ...) \
     do { \
         if (bf16) LAUNCH(ctx, kid, s, (kern<ElemBF16>), grid, dim3(256), 0, s, __VA_ARGS__); \
         else LAUNCH(ctx, kid, s, (kern<ElemF16>), grid, dim3(256), 0, s, __VA_ARGS__); \
     } while (0)
 
-int cfx_i_mxi8_compress(CompressCall& cc) {
-    cfx_ctx* ctx = cc.ctx;
-    hipStream_t s = (hipStream_t)cc.stream;
-    LocalLayerArgs a;
-    const int lg = cfx_i_local_layer(cc, a);
-    if (lg < 0) return lg;
-    if (lg) {
-        MXI8_LAUNCH(cc.bf16, KID_ABSMEAN_COMPRESS_GATED, k_mxi8_layer, dim3((unsigned)lg), cc.b, cc.gd, a);
-        return check_launch(ctx, "mxint8 layer launch");
-    }
-    MXI8_LAUNCH(cc.bf16, KID_TOPK_COMPRESS, k_mxi8_compress, cfx_i_local_grid(cc.N, cc.C, cc.batch), cc.b, (size_t)cc.N * cc.C, cc.flags);
-    return cfx_i_local_tail(cc, "mxint8 compress launch");
-}
-
-int cfx_i_mxi8_decompress(cfx_ctx* ctx, bool bf16, int N, int C, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val) {
-    hipStream_t s = (hipStream_t)stream;
-    MXI8_LAUNCH(bf16, KID_TOPK_DECOMPRESS, k_mxi8_decompress, cfx_i_local_grid(N, C, batch), b, (size_t)N * C, pre, pre_val);
-    return check_launch(ctx, "decompress launch");
-}
+LOCAL_FAMILY_HOST(mxi8, "mxint8", MXI8_LAUNCH)

@@ -232,7 +232,8 @@ int cfx_plan_add_compress_ex(cfx_plan* p, int codec, int N, int C, int param, in
     if (n_ride < 0 || n_ride > CFX_MAX_BATCH || (n_ride && !ride)) return fail(p->ctx, CFX_ERR_BATCH, "plan: ride-along batch out of range");
     bool bf16 = false;
     const int id = codec_id(codec, &bf16);
-    if (n_ride && id != CFX_CODEC_BINARY) return fail(p->ctx, CFX_ERR_CODEC, "plan: ride-along reconstruction items need the 1-bit codec");
+    const CfxCodec* k = cfx_i_codec(id);
+    if (n_ride && !(k && k->ride)) return fail(p->ctx, CFX_ERR_CODEC, "plan: ride-along reconstruction items need the 1-bit codec");
     if (!id && codec >= 0x100) return fail(p->ctx, CFX_ERR_CODEC, "plan: no such codec / element type");
     if (!shape_ok(codec, N, C, param)) return fail(p->ctx, CFX_ERR_SHAPE, "plan: bad codec/shape");
     PlanOp* o = plan_push(p);
@@ -455,8 +456,8 @@ int cfx_plan_set_second_order(cfx_plan* p, int op, int n_comp, const cfx_second_
     if (n_comp != want_comp || n_rec != want_rec) return fail(p->ctx, CFX_ERR_BATCH, "plan: second-order states: one per compress item and one per reconstruction item of the op");
     if ((n_comp && !comp_second) || (n_rec && !rec_second)) return fail(p->ctx, CFX_ERR_NULL, "plan: null second-order states");
     bool bf16 = false;
-    const int id = codec_id(o->codec, &bf16);
-    if ((id != CFX_CODEC_BINARY && id != CFX_CODEC_INT2) || bf16 || (o->flags & CFX_FLAG_NO_EF) || o->n_ride || (kind == 0 && o->n_gated))
+    const CfxCodec* k = cfx_i_codec(codec_id(o->codec, &bf16));
+    if (!(k && k->second_order) || bf16 || (o->flags & CFX_FLAG_NO_EF) || o->n_ride || (kind == 0 && o->n_gated))
         return fail(p->ctx, CFX_ERR_CODEC, "plan: second-order states need the 1-bit or 2-bit codec, fp16, no CFX_FLAG_NO_EF, no ride-along / gated items");
     const bool upd = (o->flags & CFX_FLAG_UPDATE_CACHE) != 0;
     for (int i = 0; i < n_comp; ++i) {

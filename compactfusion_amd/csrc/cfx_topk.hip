@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void k_topk_decompress(BatchD batch, size_t E,
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
 // one of the five instantiations of a kernel template (param validated: 1, 2, 4, 8 or 16)
-#define TOPK_LAUNCH(m, kid, kern, grid, ...) \
+#define TOPK_LAUNCH(bf16, m, kid, kern, grid, ...) \
     do { \
         switch (m) { \
             case 1: LAUNCH(ctx, kid, s, kern<1>, grid, dim3(256), 0, s, __VA_ARGS__); break; \
@@ -153,22 +153,4 @@ __global__ __launch_bounds__(256) void k_topk_decompress(BatchD batch, size_t E,
         } \
     } while (0)
 
-int cfx_i_topk_compress(CompressCall& cc) {
-    cfx_ctx* ctx = cc.ctx;
-    hipStream_t s = (hipStream_t)cc.stream;
-    LocalLayerArgs a;
-    const int lg = cfx_i_local_layer(cc, a);
-    if (lg < 0) return lg;
-    if (lg) {
-        TOPK_LAUNCH(cc.param, KID_ABSMEAN_COMPRESS_GATED, k_topk_layer, dim3((unsigned)lg), cc.b, cc.gd, a);
-        return check_launch(ctx, "topk layer launch");
-    }
-    TOPK_LAUNCH(cc.param, KID_TOPK_COMPRESS, k_topk_compress, cfx_i_local_grid(cc.N, cc.C, cc.batch), cc.b, (size_t)cc.N * cc.C, cc.flags);
-    return cfx_i_local_tail(cc, "topk compress launch");
-}
-
-int cfx_i_topk_decompress(cfx_ctx* ctx, int N, int C, int param, int batch, const BatchD& b, void* stream, unsigned* pre, unsigned pre_val) {
-    hipStream_t s = (hipStream_t)stream;
-    TOPK_LAUNCH(param, KID_TOPK_DECOMPRESS, k_topk_decompress, cfx_i_local_grid(N, C, batch), b, (size_t)N * C, pre, pre_val);
-    return check_launch(ctx, "decompress launch");
-}
+LOCAL_FAMILY_HOST(topk, "topk", TOPK_LAUNCH)

@@ -47,3 +47,21 @@ def test_one_bit_layer_kernel_leaves_room_for_a_collective_kernel(rows):
     assert ks
     for k in ks:
         assert k["vgpr"] <= 104 or k["demangled"].endswith("true>"), k      # (the <.., true> instantiation carries the developer stamps)
+
+
+def test_every_kernel_compiles_to_what_it_did_before_the_codec_table(rows):
+    """The codec table (csrc/cfx_api.hip codec_table) and the block-local families' shared host tail moved HOST code only:
+    tests/golden/resource_rows_codec_table_parent.json is collect() at the commit before them, every kernel of the library.  SGPR counts are
+    in the fixture and not asserted: they do not bound the occupancy of these kernels."""
+    import json
+    with open(os.path.join(REPO, "tests", "golden", "resource_rows_codec_table_parent.json")) as f:
+        parent = {(p["file"], p["demangled"]): p for p in json.load(f)}
+    assert len(parent) == 192
+    cur = {}
+    for k in rows:
+        assert (k["file"], k["demangled"]) not in cur, k
+        cur[k["file"], k["demangled"]] = k
+    assert set(cur) == set(parent), (sorted(set(parent) - set(cur)), sorted(set(cur) - set(parent)))
+    for key, p in parent.items():
+        for field in ("vgpr", "agpr", "lds", "scratch", "occupancy"):
+            assert cur[key].get(field, 0) == p.get(field, 0), (field, p, cur[key])

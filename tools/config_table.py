@@ -87,7 +87,7 @@ def alg_pair(cid, param=0):
     if cid == 16:
         pkt = 1 + 1.0 / 32
         return 6 + pkt, 4 + pkt
-    if cid in (10, 12, 14):
+    if cid in K.CODEC_TABLE and K.CODEC_TABLE[cid].setting:      # block-scaled with a block size B = param
         pkt = {10: 0.125, 12: 0.25, 14: 0.375}[cid] + 2.0 / param
         return 6 + pkt, 4 + pkt
     return ALG[cid]
