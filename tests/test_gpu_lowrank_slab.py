@@ -26,20 +26,9 @@ def subspace_iter_fp64(D, Q0, iters=2):
 
 def make(N, C, rank, seed, decay=0.7, resid_rank=None):
     """x, base with a residual of decaying spectrum (sigma_k = decay^k) over `resid_rank` directions (default min(N, 48)) plus a
-    little noise, and the start matrix."""
-    from compactfusion_amd import codecs as K
-    g = torch.Generator().manual_seed(seed)
-    k = resid_rank or min(N, 48)
-    L = torch.linalg.qr(torch.randn(N, k, generator=g))[0]
-    R = torch.linalg.qr(torch.randn(C, k, generator=g))[0]
-    s = decay ** torch.arange(k, dtype=torch.float32)
-    D = (L * s) @ R.t() * (N * C) ** 0.5 * 0.05
-    if resid_rank is None:
-        D = D + 1e-3 * torch.randn(N, C, generator=g)
-    base = torch.randn(N, C, generator=g).half()
-    x = (base.float() + D).half()
-    q0 = torch.zeros(C, K.lr_rank_pad(rank))
-    q0[:, :rank] = torch.linalg.qr(torch.randn(C, rank, generator=g))[0]
+    little noise, and the start matrix: tests/_lr_sender_cases.py graded(), on the device."""
+    import _lr_sender_cases as SC
+    x, base, q0 = SC.graded(N, C, rank, seed, decay=decay, resid_rank=resid_rank)
     return x.cuda(), base.cuda(), q0.cuda()
 
 
