@@ -62,6 +62,9 @@ SYMBOLS = [
     ("cfx_set_fused_finalize", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("cfx_set_stats_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("cfx_set_gated_launch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("cfx_set_captured_layer", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("cfx_captured_layer_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    ("cfx_captured_layer_release", ctypes.c_int, [ctypes.c_void_p]),
     ("cfx_set_lr_chain", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("cfx_set_lr_decode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("cfx_hw_queues_ok", ctypes.c_int, []),

@@ -72,7 +72,45 @@ def context(device: int):
             if rc != 0:
                 raise CfxError("cfx_prepare failed: " + (lib.cfx_last_error_string(c) or b"").decode())
         _ctx[device] = c
+        if torch.cuda.is_available() and _captured_layer_setting():
+            set_captured_layer(_captured_layer_setting(), device)
     return c
+
+
+def _captured_layer_setting() -> int:
+    from . import config
+    n = int(config.get("captured_layer"))
+    if n < 0:
+        raise ValueError(f"captured_layer must be 0 .. 4096 (got {n})")
+    return n
+
+
+def set_captured_layer(slots: int, device: Optional[int] = None) -> None:
+    """The context's pool of private gate slots for the block-local codecs' layer launch under hipGraph capture (include/cfx.h,
+    cfx_set_captured_layer): 0 = a captured layer call is compress ; reconstruct (default), n = up to n captured layer calls stay ONE
+    launch.  Allocates; call it outside a capture.  ValueError: out of range, or slots are handed out to captured graphs."""
+    device = torch.cuda.current_device() if device is None else device
+    ctx = context(device)
+    _check(ctx, _lib.load().cfx_set_captured_layer(ctx, int(slots)), "set_captured_layer")
+
+
+def captured_layer_stats(device: Optional[int] = None) -> dict:
+    """How many capture-time layer calls of the context took the one-launch form / the sequence, and the slots still free."""
+    import ctypes
+    device = torch.cuda.current_device() if device is None else device
+    ctx = context(device)
+    one, seq, free = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check(ctx, _lib.load().cfx_captured_layer_stats(ctx, ctypes.byref(one), ctypes.byref(seq), ctypes.byref(free)), "captured_layer_stats")
+    return {"one_launch": one.value, "sequence": seq.value, "slots_free": free.value}
+
+
+def apply_captured_layer() -> None:
+    """configure(captured_layer=...) onto every context that exists (compact_init / compact_reset; a new context takes it when created)"""
+    if not torch.cuda.is_available():
+        return
+    n = _captured_layer_setting()
+    for device in list(_ctx):
+        set_captured_layer(n, device)
 
 
 def set_fused_finalize(on: bool, device: Optional[int] = None) -> None:

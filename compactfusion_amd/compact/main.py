@@ -61,6 +61,7 @@ def compact_init(config: CompactConfig):
     _generation += 1
     _drop_kv_exchanges()
     _config = config
+    codecs.apply_captured_layer()
     _cache = CompactCache(quantize=config.quantized_cache)
     _step = None
     if config.override_with_patch_gather_fwd:
@@ -78,6 +79,7 @@ def compact_reset():
     global _cache, _step, _allgather_cache, _current_cache_key, _generation
     _generation += 1
     _drop_kv_exchanges()
+    codecs.apply_captured_layer()
     _cache = CompactCache(quantize=_config.quantized_cache)
     from .stats import stats_clear
     stats_clear()

@@ -37,6 +37,10 @@ int2_block             CFX_INT2_BLOCK                32 | 64 | 128 - block size 
                                                      that share one fp16 scale (64); read when a layer is (re)built
 int3_block             CFX_INT3_BLOCK                32 | 64 | 128 - block size of COMPACT_COMPRESS_TYPE.INT3_BLOCK (native codec 14): elements of a row
                                                      that share one fp16 scale (64); read when a layer is (re)built
+captured_layer         CFX_CAPTURED_LAYER            0 .. 4096 - private gate slots of a context for the block-local codecs' layer launch under hipGraph
+                                                     capture (include/cfx.h, cfx_set_captured_layer): 0 (default) = a captured layer call is
+                                                     compress ; reconstruct, n = up to n captured layer calls stay ONE launch; applied when a
+                                                     context is created and by compact_init / compact_reset
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process
 """
@@ -59,6 +63,7 @@ _SETTINGS = {
     "binary_block": ("CFX_BINARY_BLOCK", "64", ("32", "64", "128")),
     "int2_block": ("CFX_INT2_BLOCK", "64", ("32", "64", "128")),
     "int3_block": ("CFX_INT3_BLOCK", "64", ("32", "64", "128")),
+    "captured_layer": ("CFX_CAPTURED_LAYER", "0", None),
 }
 _explicit: Dict[str, str] = {}
 

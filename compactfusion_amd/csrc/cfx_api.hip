@@ -289,6 +289,8 @@ cfx_ctx* cfx_create(int device) {
     c->fused = 1;
     c->stats_rows = 0;
     c->gated_on = 1;
+    c->cap_pool = nullptr;
+    c->cap_n = c->cap_used = c->cap_one = c->cap_seq = 0;
     c->lr_chain = c->lr_decode = 0;
     c->dev_probe = 0;
     c->dev_scale_split = 0;
@@ -423,6 +425,7 @@ void cfx_destroy(cfx_ctx* ctx) {
     if (!ctx) return;
     prof_free(ctx);
     if (ctx->tick) (void)hipFree(ctx->tick);
+    cfx_i_cap_destroy(ctx);
     for (int i = 0; i < ctx->lrs_n; ++i)
         if (ctx->lrs_arena[i]) (void)hipFree(ctx->lrs_arena[i]);
     for (int i = 0; i < CFX_RING_STREAMS; ++i)
@@ -678,9 +681,11 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     // numbers that have gone by - so a capturing stream gets the capturable sequence instead, from this very call: compress (tickets that
     // reset themselves) ; reconstruct the gated items in stream order (an exchange-layer op: the caller's exchange in between, xg->taken
     // stays 0).  Bit-identical results; two (int4 / int8: three) launches per layer instead of one, and no host call per replay.
-    // (Device-side counters would keep the one-launch form capturable: every workgroup of a launch has to read the launch's number and
-    // exactly one has to advance it once ALL have read it - the last workgroup to leave, an exit ticket per workgroup - and the gate
-    // blocks have to be reset by it as well: ~0.5 us on every launch of the headline path for a mode the plan replay does not need.)
+    // (Device-side counters would keep the abs-mean and min/max one-launch forms capturable only with an exit ticket per workgroup, a last
+    // leaver that advances the launch's number and a gate-block reset on every launch of the headline path: not built.  The block-local
+    // families need none of that - counters that only grow give every workgroup its launch's number - and have a capturable layer launch
+    // behind cfx_set_captured_layer: cfx_capture.hip, taken by their cfx_i_*_compress below this call.  Measured, it does not beat the
+    // sequence under a graph, so the switch is off by default.)
     bool capturing = false;
     if (n_gated || xg) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -693,7 +698,10 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     cc.ws = ws; cc.wstride = wstride; cc.CB = CB; cc.upd = upd; cc.capturing = capturing; cc.bf16 = bf16;
     cc.fused = false; cc.tick = nullptr; cc.slot = 0; cc.stream_cus = 0; cc.R = cc.P = 0;
     cc.second = second; cc.decay = decay;
-    if (!k->tiled) return k->compress(cc);
+    // (cfx_captured_layer_stats: a capture-time layer call that did not take the capturable one-launch form took the sequence)
+    const int cap_one = ctx->cap_one;
+    auto counted = [&](int rc) { if (capturing && rc == CFX_OK && ctx->cap_one == cap_one) ++ctx->cap_seq; return rc; };
+    if (!k->tiled) return counted(k->compress(cc));
 
     // the abs-mean and min/max families: statistics + finalize: ONE launch with the in-launch finalize (default), or the two-kernel sequence
     const bool fused = ctx->fused && CB <= TICK_MAX_CB;
@@ -713,7 +721,7 @@ static int compress_impl(cfx_ctx* ctx, int codec_arg, int N, int C, int param, i
     const int R = fused ? fused_rows(ctx, N, C, batch, stream_cus) : auto_rows(ctx, N, C, batch, true);
     const int P = (N + R - 1) / R;
     cc.fused = fused; cc.tick = tick; cc.slot = slot; cc.stream_cus = stream_cus; cc.R = R; cc.P = P;
-    return k->compress(cc);
+    return counted(k->compress(cc));
 }
 
 int cfx_compress_batch_ex(cfx_ctx* ctx, int codec, int N, int C, int param, int flags, int batch, const cfx_comp_item* items,
@@ -752,7 +760,8 @@ int cfx_gate_recover(cfx_ctx* ctx) {
     if (cur != ctx->device && hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CFX_ERR_LAUNCH, "gate_recover: hipSetDevice failed");
     int rc = 0;
     const size_t words = (size_t)((char*)ctx->colgate - (char*)ctx->tick) / sizeof(unsigned);      // ticket blocks + gate blocks
-    if (hipDeviceSynchronize() != hipSuccess || hipMemset(ctx->tick, 0, words * sizeof(unsigned)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    if (hipDeviceSynchronize() != hipSuccess || hipMemset(ctx->tick, 0, words * sizeof(unsigned)) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        cfx_i_cap_recover(ctx) != CFX_OK) {       // (the captured layer launches' slots: all-zero is launch 0, live graphs stay valid)
         (void)hipGetLastError();
         rc = fail(ctx, CFX_ERR_LAUNCH, "gate_recover: cannot reset the ticket / gate blocks");
     } else {

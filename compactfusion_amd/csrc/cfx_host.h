@@ -20,7 +20,8 @@ struct CompressCall {
     size_t wstride;
     int CB;
     bool bf16;                       // the call's tensors (x, base, new_base, recon) are bf16: CFX_ELEM_BF16 on the codec argument
-    bool upd, capturing;             // capturing: the stream is under hipGraph capture - no one-launch layer form (include/cfx.h)
+    bool upd, capturing;             // capturing: the stream is under hipGraph capture - no eager one-launch layer form (include/cfx.h; the
+                                     // block-local families: the capturable one on a private gate slot, cfx_capture.hip, where a pool has one)
     // the tile geometry of the abs-mean and min/max families' compress launches (compress_impl, before the dispatch)
     bool fused;
     unsigned* tick;

@@ -94,6 +94,10 @@ struct cfx_ctx {
     void* dev_buf;                  // cfx_dev_stamps (developer build): where the probes write
     int stats_rows;                 // cfx_set_stats_rows: override of the statistics tile height (experiments), 0 = automatic
     int gated_on;                   // cfx_set_gated_launch: 1 (default) the one-launch gated / exchange-layer forms where they qualify
+    // cfx_set_captured_layer (cfx_capture.hip): the pool of private gate slots of the capturable layer launches - cap_n slots of
+    // CFX_CAP_SLOT_WORDS words, the first cap_used handed out to graph nodes - and how many capture-time layer calls took which form
+    unsigned* cap_pool;
+    int cap_n, cap_used, cap_one, cap_seq;
     int lr_chain, lr_decode;        // cfx_set_lr_chain / cfx_set_lr_decode (0 = automatic)
     int dev_probe;                  // cfx_set_dev_probe (developer builds)
     int dev_scale_split;            // cfx_dev_set_probe(CFX_DEV_SCALE_SPLIT + s) (developer builds): 0 = the library's choice
@@ -189,6 +193,11 @@ struct CfxCodec {
     int (*decompress)(const DecompressCall& dc);
 };
 CFX_HIDDEN const CfxCodec* cfx_i_codec(int id);      // the row of codec `id`, NULL: no such codec
+// cfx_capture.hip: a block-local family's layer call on a capturing stream (1: the capturable layer kernel is enqueued; 0: not that form;
+// < 0: an error code); the pool re-zeroed by cfx_gate_recover / freed by cfx_destroy
+CFX_HIDDEN int cfx_i_captured_layer(CompressCall& cc);
+CFX_HIDDEN int cfx_i_cap_recover(cfx_ctx* ctx);
+CFX_HIDDEN void cfx_i_cap_destroy(cfx_ctx* ctx);
 
 // A `codec` argument of the ABI -> the codec id and the element type of the call's tensors (CFX_ELEM_BF16, include/cfx.h).  0 - no codec -
 // for any other high bit and for the bf16 bit on a codec that has no bf16 form.

@@ -186,6 +186,10 @@ inline int cfx_i_local_tail(CompressCall& cc, const char* what) {
         cfx_ctx* ctx = cc.ctx; \
         hipStream_t s = (hipStream_t)cc.stream; \
         LocalLayerArgs a; \
+        if (cc.capturing) {                 /* a pool of private gate slots (cfx_set_captured_layer): ONE capturable launch, cfx_capture.hip */ \
+            const int cl = cfx_i_captured_layer(cc); \
+            if (cl) return cl < 0 ? cl : CFX_OK; \
+        } \
         const int lg = cfx_i_local_layer(cc, a); \
         if (lg < 0) return lg; \
         if (lg) { \

@@ -354,7 +354,14 @@ int cfx_compress_batch_ex(cfx_ctx* ctx, int codec, int N, int C, int param, int 
  * layer call and the peer-to-peer layer op four times between eager launches of the same context.  The ungated launches (cfx_compress_batch
  * / _ex) are capturable as they are.  (An int4 / int8 compress call outside a capture runs as ONE launch too - statistics, scales, codes
  * and the state update from the tile in registers, k_minmax_layer - handing its partials over as sequence-tagged words in an arena the
- * context keeps per stream; under stream capture the same call runs the capturable sequence statistics ; quantise, with identical results.) */
+ * context keeps per stream; under stream capture the same call runs the capturable sequence statistics ; quantise, with identical results.)
+ * ONE launch under capture (cfx_set_captured_layer below, off by default): the BLOCK-LOCAL codecs - top-k, MXFP4, BINARY_BLOCK, INT2_BLOCK,
+ * INT3_BLOCK, MXINT8 - wait for nothing but "packets complete" (and the external gate), so their layer launch can derive its number on
+ * the device: each captured layer call takes a private gate slot from a pool of the context, group S's arrivals and an entry ticket per
+ * group-D workgroup are 64-bit fetch-adds on counters of that slot that only ever grow, launch number = counter / workgroups per launch,
+ * and the gate opens at number + 1 - nothing is advanced or reset by anybody (csrc/cfx_capture_gate.h, csrc/cfx_capture.hip: separate
+ * kernel instantiations, same bits; no eager launch changed).  The abs-mean and min/max layer launches (codecs 1 - 4, 6) carry
+ * host-advanced launch tags in their hand-over words and always take the sequence under capture. */
 int cfx_compress_batch_gated(cfx_ctx* ctx, int codec, int N, int C, int param, int flags,
                              int batch, const cfx_comp_item* items, int n_ride, const cfx_decomp_item* ride,
                              int n_gated, const cfx_decomp_item* gated,
@@ -398,6 +405,30 @@ int cfx_set_stats_rows(cfx_ctx* ctx, int rows);
 int cfx_set_gated_launch(cfx_ctx* ctx, int on);
 int cfx_set_lr_chain(cfx_ctx* ctx, int chain);
 int cfx_set_lr_decode(cfx_ctx* ctx, int mode);
+/* The block-local codecs' layer launch as ONE launch under hipGraph capture ("Stream capture" above).
+ *   cfx_set_captured_layer(ctx, slots)   0 (default): a captured layer call enqueues the capturable sequence, as ever.  n in 1 .. 4096 (the
+ *       maximum; 4224 bytes of device memory a slot): allocates and zeroes a pool of n private gate slots with their ticket lines - here,
+ *       because nothing may be allocated during capture; call it outside a capture.  A negative value, one above 4096, or a CHANGE of the
+ *       pool's size while slots are handed out is CFX_ERR_SHAPE (the same value again is CFX_OK and changes nothing).
+ *   With a pool, a layer call on a CAPTURING stream takes a slot and enqueues the one capturable layer kernel when the codec is one of the
+ *       six block-local families, the conditions of the eager one-launch form hold (gated items, cfx_set_gated_launch on, a stream of >= 128
+ *       CUs, loop-back items that read this launch's packets - or the op is a peer-to-peer exchange-layer op, whose exchange runs inside the
+ *       launch) and a slot is free: cfx_compress_batch_gated, and cfx_plan_run for cfx_plan_add_exchange_layer (no communicator) and
+ *       cfx_plan_add_exchange_layer_p2p ops.  Every other case - no pool, no free slot, another codec, an exchange-layer op with a
+ *       communicator - enqueues the capturable sequence with identical results.
+ *   RULE: a slot belongs to ONE captured graph node, for as long as the graph may be replayed; every launch on a slot is that node, so the
+ *       counters of the slot say which replay is running.  Replays of the graphs of one context must be stream-ordered against each other
+ *       and against the context's other launches on the same buffers, as for workspaces.  Only loop-back items and world size 1 are covered
+ *       under capture: with live peers the packet-slot parity and the group's health are host state a graph would bake in.
+ *   cfx_captured_layer_stats   how many capture-time layer calls of the context took the one-launch form / the sequence (every codec's
+ *       gated and exchange-layer calls count), and how many slots are free; any pointer may be NULL.
+ *   cfx_captured_layer_release hands every slot back, zeroed, after a device synchronisation - for a caller that has DESTROYED its graphs
+ *       (a surviving graph would share its slot with the next capture).
+ *   cfx_gate_recover zeroes the pool as well: all-zero is "before launch 0", so live graphs stay valid.  A wait that gives up has drawn its
+ *       ticket and group S always arrives, so a time-out leaves a slot consistent even without it. */
+int cfx_set_captured_layer(cfx_ctx* ctx, int slots);
+int cfx_captured_layer_stats(cfx_ctx* ctx, int* one_launch, int* sequence, int* slots_free);
+int cfx_captured_layer_release(cfx_ctx* ctx);
 /* Flag-ordered launches (the exchange-layer ops, the exchange lane) need the streams they order to sit on hardware queues of their own:
  * a polling kernel is never scheduled out for the kernel it waits for.  HIP multiplexes streams over a pool of hardware queues; with
  * GPU_MAX_HW_QUEUES unset a stream created after a collective library initialised can be time-sliced against the exchange stream's
