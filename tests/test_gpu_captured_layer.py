@@ -14,182 +14,13 @@ import numpy as np
 import pytest
 import torch
 
-import bblock_contract as BB
 import bf16_contract as BC
-import int2block_contract as I2
-import int3block_contract as I3
-import mxfp4_contract as MX
 import mxint8_contract as M8
-from _gpu_codec import host, oracle as ref_oracle
-from oracle import ref_np as R
+from _captured_layer import (FAMILIES, KERNEL_NODE, SHAPES, Hip, Layer, _clean_pool, _ctx, capture, dev, eager, same, set_pool,  # noqa: F401
+                             shape_of, stats)
+from _gpu_codec import host
 
 pytestmark = pytest.mark.gpu
-
-F16 = np.float16
-ELEM_BF16 = 0x100
-NB, NP = 2, 4
-SHAPES = [(4, 128), (8, 4224)]
-
-
-def _mx_step(x, st):
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        pkt, nb = MX.residual_compress(x.view(F16), st.view(F16), True)
-    return np.asarray(pkt).view(np.uint16), R.bits(nb)
-
-
-def _topk_step(x, st):
-    N, C = x.shape
-    return ref_oracle("topk", x.view(F16), st.view(F16), 8, N, C)
-
-
-# name -> (codec id, param, bf16, one residual compress on bit patterns: (x, state) -> (packet words, new state bits))
-FAMILIES = {"topk8": (5, 8, False, _topk_step), "mxfp4": (MX.CID, 0, False, _mx_step)}
-for _B in (32, 128):
-    for _bf in (False, True):
-        _e = "bf16" if _bf else "fp16"
-        FAMILIES[f"bb{_B}-{_e}"] = (BB.CID, _B, _bf, lambda x, st, B=_B, bf=_bf: BB.step(x, st, B, bf))
-        FAMILIES[f"i2b{_B}-{_e}"] = (I2.CID, _B, _bf, lambda x, st, B=_B, bf=_bf: I2.step(x, st, B, bf))
-        FAMILIES[f"i3b{_B}-{_e}"] = (I3.CID, _B, _bf, lambda x, st, B=_B, bf=_bf: I3.step(x, st, B, bf))
-for _bf in (False, True):
-    FAMILIES["mxi8-" + ("bf16" if _bf else "fp16")] = (M8.CID, 0, _bf, lambda x, st, bf=_bf: M8.step(x, st, bf))
-
-
-def shape_of(fam, shape):
-    return (8, 128) if fam == "topk8" and shape == (4, 128) else shape        # the nearest shape top-k accepts: still 1 S and 1 D workgroup
-
-
-def dev(u16, bf):
-    t = torch.from_numpy(np.ascontiguousarray(u16).view(np.int16))
-    return t.view(torch.bfloat16 if bf else torch.float16).cuda()
-
-
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.shape == want.shape, what
-    bad = got != want
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} words differ (first at {int(np.argmax(bad))})"
-
-
-def _ctx():
-    from compactfusion_amd import _lib, codecs as K
-    return _lib.load(), K.context(0)
-
-
-def stats():
-    from compactfusion_amd import codecs as K
-    s = K.captured_layer_stats(0)
-    return s["one_launch"], s["sequence"], s["slots_free"]
-
-
-def set_pool(n):
-    lib, ctx = _ctx()
-    assert lib.cfx_set_captured_layer(ctx, n) == 0, lib.cfx_last_error_string(ctx)
-
-
-@pytest.fixture(autouse=True)
-def _clean_pool():
-    """every test starts and ends with no pool, no slot handed out and the default switches (its graphs are gone when it returns)"""
-    from compactfusion_amd import config
-    lib, ctx = _ctx()
-
-    def clean():
-        gc.collect()
-        torch.cuda.synchronize()
-        assert lib.cfx_captured_layer_release(ctx) == 0
-        assert lib.cfx_set_captured_layer(ctx, 0) == 0
-        assert lib.cfx_set_gated_launch(ctx, 1) == 0
-    clean()
-    yield
-    config.reset()
-    clean()
-
-
-class Layer:
-    """one layer call - cfx_compress_batch_gated or the peer-to-peer exchange-layer op (no live peer) - on static buffers: NB own tensors
-    with error feedback in place, NP looped-back peers; the oracle's packets and states advance with every step()"""
-
-    def __init__(self, fam, N, C, seed, op="gated"):
-        from compactfusion_amd import _lib, codecs as K
-        self.lib, self.ctx = _ctx()
-        self.cid, self.param, self.bf, self.fn = FAMILIES[fam]
-        self.N, self.C, self.op, self.fam = N, C, op, fam
-        self.cabi = self.cid | (ELEM_BF16 if self.bf else 0)
-        self.rng = np.random.default_rng(seed)
-        self.nbytes = K.packet_bytes(self.cabi, N, C, self.param)
-        assert self.nbytes > 0, (fam, N, C)
-        base = self.fresh()
-        self.xin = [dev(b, self.bf) for b in base]
-        self.own = [dev(b, self.bf) for b in base]
-        self.peer = [dev(base[g % NB], self.bf) for g in range(NP)]
-        self.want = [b.copy() for b in base]
-        self.wpk = [None] * NB
-        slot = (self.nbytes + 255) // 256 * 256
-        self.pk = torch.zeros(NB, slot, dtype=torch.uint8, device="cuda")
-        self.comp = (_lib.CompItem * NB)(*[_lib.CompItem(self.xin[i].data_ptr(), self.own[i].data_ptr(), self.own[i].data_ptr(),
-                                                         self.pk[i].data_ptr()) for i in range(NB)])
-        self.gated = (_lib.DecompItem * NP)(*[_lib.DecompItem(self.pk[g % NB].data_ptr(), self.peer[g].data_ptr(), self.peer[g].data_ptr())
-                                              for g in range(NP)])
-        self.plan = None
-        if op == "p2p_layer":
-            self.flag = torch.zeros(64, dtype=torch.int32, device="cuda")
-            self.plan = self.lib.cfx_plan_create(self.ctx)
-            rc = self.lib.cfx_plan_add_exchange_layer_p2p(self.plan, self.cabi, N, C, self.param, _lib.FLAG_UPDATE_CACHE, NB, self.comp, NP,
-                                                          self.gated, self.flag.data_ptr(), 0, (ctypes.c_void_p * 1)(), None, 0)
-            assert rc >= 0 and self.lib.cfx_plan_finalize(self.plan) == 0, self.lib.cfx_last_error_string(self.ctx)
-        self.flags = _lib.FLAG_UPDATE_CACHE
-
-    def fresh(self):
-        f = [(self.rng.standard_normal((self.N, self.C)) * 0.5).astype(np.float32) for _ in range(NB)]
-        return [BC.f32_to_bf16(a) if self.bf else a.astype(F16).view(np.uint16) for a in f]
-
-    def call(self, sh):
-        if self.op == "gated":
-            rc = self.lib.cfx_compress_batch_gated(self.ctx, self.cabi, self.N, self.C, self.param, self.flags, NB, self.comp, 0, None, NP,
-                                                   self.gated, None, 0, sh)
-        else:
-            rc = self.lib.cfx_plan_run(self.plan, 0, 1, sh)
-        assert rc == 0, self.lib.cfx_last_error_string(self.ctx)
-
-    def step(self):
-        """fresh activations into the static buffers; the oracle one step on"""
-        xs = self.fresh()
-        for i in range(NB):
-            self.xin[i].copy_(dev(xs[i], self.bf))
-            pkt, nb = self.fn(xs[i].reshape(self.N, self.C), self.want[i].reshape(self.N, self.C))
-            self.wpk[i], self.want[i] = np.asarray(pkt).reshape(-1), np.asarray(nb).reshape(self.N, self.C)
-        torch.cuda.synchronize()
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        assert self.lib.cfx_gate_errors(self.ctx) == 0, what
-        for i in range(NB):
-            if self.wpk[i] is not None:
-                same(self.pk[i, :self.nbytes].cpu().numpy().view(np.uint16), self.wpk[i], f"{self.fam} {what}: packet {i}")
-            same(host(self.own[i]), self.want[i], f"{self.fam} {what}: sender state {i}")
-        for g in range(NP):
-            same(host(self.peer[g]), self.want[g % NB], f"{self.fam} {what}: peer state {g}")
-
-    def close(self):
-        if self.plan is not None:
-            self.lib.cfx_plan_destroy(self.plan)
-            self.plan = None
-
-
-def capture(side, fn):
-    side.wait_stream(torch.cuda.current_stream())
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            fn(side.cuda_stream)
-    torch.cuda.synchronize()
-    return graph
-
-
-def eager(side, layer, what):
-    layer.step()
-    with torch.cuda.stream(side):
-        layer.call(side.cuda_stream)
-    layer.check(what)
 
 
 # ---- 1: the gated call and the p2p layer op, one capture, six replays between eager launches -------------------------------------------
@@ -317,61 +148,6 @@ def test_pool_of_two_third_call_takes_the_sequence_and_release():
         torch.cuda.synchronize()
         for L in Ls:
             L.close()
-
-
-# ---- the HIP runtime torch has loaded, through ctypes: capture on a raw stream handle, the nodes of the captured graph -----------------
-class Hip:
-    def __init__(self):
-        path = None
-        with open("/proc/self/maps") as f:
-            for line in f:
-                if "libamdhip64" in line:
-                    path = line.split()[-1]
-                    break
-        assert path, "the HIP runtime is not loaded"
-        h = self.h = ctypes.CDLL(path)
-        V, P = ctypes.c_void_p, ctypes.POINTER
-        for name, args in (("hipStreamBeginCapture", [V, ctypes.c_int]), ("hipStreamEndCapture", [V, P(V)]),
-                           ("hipGraphGetNodes", [V, P(V), P(ctypes.c_size_t)]), ("hipGraphNodeGetType", [V, P(ctypes.c_int)]),
-                           ("hipGraphInstantiate", [P(V), V, P(V), ctypes.c_char_p, ctypes.c_size_t]), ("hipGraphLaunch", [V, V]),
-                           ("hipGraphExecDestroy", [V]), ("hipGraphDestroy", [V]), ("hipStreamSynchronize", [V])):
-            fn = getattr(h, name)
-            fn.argtypes, fn.restype = args, ctypes.c_int
-
-    def capture(self, sh, fn):
-        """(graph, executable graph, types of its nodes) of what fn enqueues on the stream with handle sh"""
-        V = ctypes.c_void_p
-        torch.cuda.synchronize()
-        assert self.h.hipStreamBeginCapture(V(sh), 2) == 0                    # hipStreamCaptureModeRelaxed
-        try:
-            fn(sh)
-        finally:
-            g = V()
-            rc = self.h.hipStreamEndCapture(V(sh), ctypes.byref(g))
-        assert rc == 0 and g.value
-        n = ctypes.c_size_t(0)
-        assert self.h.hipGraphGetNodes(g, None, ctypes.byref(n)) == 0
-        nodes = (V * max(1, n.value))()
-        assert self.h.hipGraphGetNodes(g, nodes, ctypes.byref(n)) == 0
-        types = []
-        for i in range(n.value):
-            t = ctypes.c_int(-1)
-            assert self.h.hipGraphNodeGetType(V(nodes[i]), ctypes.byref(t)) == 0
-            types.append(t.value)
-        ex = V()
-        assert self.h.hipGraphInstantiate(ctypes.byref(ex), g, None, None, 0) == 0 and ex.value
-        return g, ex, types
-
-    def launch(self, ex, sh):
-        assert self.h.hipGraphLaunch(ex, ctypes.c_void_p(sh)) == 0
-        assert self.h.hipStreamSynchronize(ctypes.c_void_p(sh)) == 0
-
-    def destroy(self, g, ex):
-        self.h.hipGraphExecDestroy(ex)
-        self.h.hipGraphDestroy(g)
-
-
-KERNEL_NODE = 0          # hipGraphNodeTypeKernel
 
 
 # ---- 5: what takes the sequence under capture, with identical bits ----------------------------------------------------------------------
