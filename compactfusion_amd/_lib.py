@@ -22,6 +22,8 @@ FLAG_ELEM_BF16 = 0x100   # cfx_int2_quantize only
 ELEM_BF16 = 0x100        # CFX_ELEM_BF16: or-ed into a `codec` argument - the call's tensors are bf16 (1-bit / 2-bit / block-scaled 1-bit, 2-bit and 3-bit codecs, MXINT8)
 MERGE_BSHD = 1           # cfx_attn_merge_ex `flags` (with ELEM_BF16: block_out / final_out are bf16)
 MERGE_FIRST = 2
+MERGE_OUT_F32 = 4        # cfx_attn_merge_many `flags` (with MERGE_BSHD, ELEM_BF16): out is fp32, not the element type
+MERGE_MAX_BLOCKS = 16
 
 
 class CompItem(ctypes.Structure):
@@ -167,6 +169,8 @@ SYMBOLS = [
     ("cfx_attn_merge_wait", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("cfx_attn_merge_ex", ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cfx_attn_merge_many", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
+                                          + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3),
 ]
 
 # include/cfx_dev.h: exported by the DEVELOPER library only (libcfx_dev.so, -DCFX_DEV_PROBES).  Bound when - and only when - that library

@@ -65,6 +65,78 @@ def update_out_and_lse(out: Optional[torch.Tensor], lse: Optional[torch.Tensor],
     return out, lse
 
 
+def merge_blocks(block_outs, block_lses, out_dtype=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ALL of a layer's attention blocks merged at once: block_outs[i] (B, S, H, D), block_lses[i] fp32 (B, H, S) - what
+    `block_attention` returns - -> out (B, S, H, D) in `out_dtype` (fp32 when None), lse fp32 (B, S, H, 1).  The softmax-weighted
+    combination is formed directly, not as the chain `update_out_and_lse` runs (include/cfx.h, cfx_attn_merge_many, states it rounding
+    by rounding):
+        m = max_i lse_i ;  e_i = exp(lse_i - m) ;  Z = sum_i e_i ;  out = (sum_i e_i out_i) / Z ;  lse = m + log Z
+    On the GPU - fp16 or bf16 blocks, D % 8 == 0, D <= 512, every block in the same one of the two layouts the fused SDPA op returns,
+    out_dtype fp32 or the blocks' type - this is ONE native launch.  The launch takes at most 16 blocks: more on the native path are
+    REFUSED (ValueError) - they are neither folded through a second launch, whose intermediate would round where the formula above does
+    not, nor handed to eager torch behind the caller's back.  Anything else (CPU tensors: the host-logic tests; other layouts or
+    types) runs the same direct formula in eager fp32 torch - never the chain."""
+    n = len(block_outs)
+    if n == 0 or n != len(block_lses):
+        raise ValueError(f"merge_blocks: {n} block outputs, {len(block_lses)} block lse tensors")
+    bo0 = block_outs[0]
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if bo0.is_cuda and bo0.dim() == 4 and bo0.dtype in (torch.float16, torch.bfloat16) and out_dtype in (torch.float32, bo0.dtype) \
+            and bo0.shape[-1] % 8 == 0 and bo0.shape[-1] <= 512:
+        bshd = 1 if bo0.is_contiguous() else (0 if bo0.transpose(1, 2).is_contiguous() else None)
+        if bshd is not None and all(
+                bo.shape == bo0.shape and bo.dtype == bo0.dtype and bo.device == bo0.device and bo.data_ptr() % 16 == 0
+                and (bo.is_contiguous() if bshd else bo.transpose(1, 2).is_contiguous())
+                and bl.dtype == torch.float32 and bl.is_contiguous() and bl.device == bo0.device
+                and bl.shape == (bo0.shape[0], bo0.shape[2], bo0.shape[1]) for bo, bl in zip(block_outs, block_lses)):
+            from .. import _lib
+            if n > _lib.MERGE_MAX_BLOCKS:
+                raise ValueError(f"merge_blocks: {n} blocks - the one-launch merge takes at most {_lib.MERGE_MAX_BLOCKS} "
+                                 "(configure(attn_merge='chain') merges any number)")
+            return _merge_many_native(block_outs, block_lses, bshd, out_dtype)
+    return _merge_direct([bo.to(torch.float32) for bo in block_outs],
+                         [bl.to(torch.float32).transpose(-2, -1).unsqueeze(-1) for bl in block_lses], out_dtype)
+
+
+def _merge_direct(outs, lses, out_dtype):
+    """the direct formula in eager fp32 torch: outs[i] fp32 (B, S, H, D), lses[i] fp32 (B, S, H, 1); sums in index order"""
+    m = lses[0]
+    for l in lses[1:]:
+        m = torch.maximum(m, l)
+    acc = z = None
+    for o, l in zip(outs, lses):
+        e = torch.exp(l - m)
+        acc, z = (e * o, e) if acc is None else (acc + e * o, z + e)
+    return (acc / z).to(out_dtype), m + torch.log(z)
+
+
+_merge_many_fn = None
+
+
+def _merge_many_native(block_outs, block_lses, bshd, out_dtype):
+    global _merge_many_fn
+    import ctypes
+    from .. import _lib, codecs
+    bo0 = block_outs[0]
+    n = len(block_outs)
+    B, S, H, D = bo0.shape
+    dev = bo0.device.index if bo0.device.index is not None else torch.cuda.current_device()
+    if _merge_many_fn is None:
+        _merge_many_fn = _lib.load().cfx_attn_merge_many
+    out = torch.empty((B, S, H, D), dtype=out_dtype, device=bo0.device)
+    lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=bo0.device)
+    ctx = codecs.context(dev)
+    flags = (_lib.MERGE_BSHD if bshd else 0) | (_lib.ELEM_BF16 if bo0.dtype == torch.bfloat16 else 0) \
+        | (_lib.MERGE_OUT_F32 if out_dtype == torch.float32 else 0)
+    P = ctypes.c_void_p * n
+    rc = _merge_many_fn(ctx, n, P(*[t.data_ptr() for t in block_outs]), P(*[t.data_ptr() for t in block_lses]), B, S, H, D, flags,
+                        out.data_ptr(), lse.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        codecs._check(ctx, rc, "cfx_attn_merge_many")
+    return out, lse
+
+
 def flag_wait(wait, device) -> None:
     """A stand-alone wait launch on the current stream for (flag address, epoch) - what `update_out_and_lse(wait=...)` folds into
     its merge launch when it can."""

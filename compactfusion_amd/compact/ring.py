@@ -26,7 +26,7 @@ from .. import config as _settings
 from ..collector import collector as _collector_mod
 from ..prof import Profiler
 from . import main as cm
-from .attention import block_attention, update_out_and_lse
+from .attention import block_attention, flag_wait, merge_blocks, update_out_and_lse
 from .main import compact_cache, compact_compress, compact_config, compact_decompress
 from .utils import COMPACT_COMPRESS_TYPE
 
@@ -261,6 +261,7 @@ class _SteadyLayer:
     """What `_gather_schedule` established for a layer, frozen: valid while the config object, the state arena generation, the
     codec and the tensor geometry stay what they were (any change falls back to the general path, which re-binds)."""
     _fast = None                 # `_fast_ok`'s answer, once asked
+    _fwait = None                # cfx_flag_wait, bound at the first attn_merge="once" call of a lane form
 
     def __init__(self, ex, q, k, v, ctype, cfg, rank, world):
         cache = compact_cache()
@@ -354,8 +355,14 @@ class _SteadyLayer:
         (`_fast_ok`; fp16 and bf16): the step is host-bound long before it is GPU-bound (8 attention + 8 merge calls per layer), so the
         fused SDPA op and the merge (`cfx_attn_merge_ex`) are called directly, on cached transposed views of the peers' states, and the
         merge launch of the last block writes the result in q.dtype itself - no cast launch behind it; otherwise block_attention +
-        update_out_and_lse and the cast."""
+        update_out_and_lse and the cast.
+        configure(attn_merge="once"): no running out / lse - the blocks' results are kept and ONE launch (`merge_blocks`,
+        cfx_attn_merge_many) merges them after block W-1, writing q.dtype; on the lane forms the wait the merge of block s carried is a
+        stand-alone cfx_flag_wait behind block s (s < W-1), issue(s, lean) is called where it always was, and what is returned has the
+        chain's types, shapes and views."""
         last = self.world - 1
+        if _settings.get("attn_merge") == "once":
+            return self._blocks_once(q, k, v, softmax_scale, sh, issue, flag, epoch)
         if self._fast_ok(q):
             sdpa, merge, ctx, mflags = self._sdpa, self._merge, self._ctx, self._mflags
             B, S, H, D = q.shape
@@ -388,6 +395,37 @@ class _SteadyLayer:
                     wait = (flag(s + 1), epoch)
             out, lse = update_out_and_lse(out, lse, bo, bl, wait)
         return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
+
+    def _blocks_once(self, q, k, v, softmax_scale, sh, issue, flag, epoch):
+        """`_blocks` with configure(attn_merge="once"): the lean path and the general one"""
+        last = self.world - 1
+        outs, lses = [], []
+        if self._fast_ok(q):
+            sdpa, ctx = self._sdpa, self._ctx
+            if self._fwait is None:
+                from .. import _lib
+                self._fwait = _lib.load().cfx_flag_wait
+            qt = q.transpose(1, 2)
+            for s, kt, vt in [(0, k.transpose(1, 2), v.transpose(1, 2))] + self._peer_t:
+                res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
+                outs.append(res[0].transpose(1, 2))
+                lses.append(res[1])
+                if issue is not None:
+                    issue(s, True)
+                    if s < last and self._fwait(ctx, flag(s + 1), epoch, sh) != 0:
+                        from .. import _lib
+                        raise RuntimeError("cfx_flag_wait failed: " + (_lib.load().cfx_last_error_string(ctx) or b"").decode())
+        else:
+            for s, kk, vv in [(0, k, v)] + self._peers:
+                bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
+                outs.append(bo)
+                lses.append(bl)
+                if issue is not None:
+                    issue(s, False)
+                    if s < last:
+                        flag_wait((flag(s + 1), epoch), q.device)
+        out, lse = merge_blocks(outs, lses, q.dtype)
+        return out, lse.squeeze(dim=-1).transpose(1, 2), None
 
 
 def _exchange_stream(device) -> "torch.cuda.Stream":

@@ -41,6 +41,11 @@ captured_layer         CFX_CAPTURED_LAYER            0 .. 4096 - private gate sl
                                                      capture (include/cfx.h, cfx_set_captured_layer): 0 (default) = a captured layer call is
                                                      compress ; reconstruct, n = up to n captured layer calls stay ONE launch; applied when a
                                                      context is created and by compact_init / compact_reset
+attn_merge             CFX_ATTN_MERGE                chain | once - how a steady layer of compact_fwd merges its W attention blocks: chain (default) = one
+                                                     merge launch per block into a running fp32 out / lse (cfx_attn_merge_ex); once = the SDPA
+                                                     results are kept and ONE launch merges them after the last block (cfx_attn_merge_many, at
+                                                     most 16 blocks), the lane forms' "next peer reconstructed" waits becoming stand-alone
+                                                     cfx_flag_wait launches.  The relay schedule and a layer's first (binding) call keep the chain
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process
 """
@@ -64,6 +69,7 @@ _SETTINGS = {
     "int2_block": ("CFX_INT2_BLOCK", "64", ("32", "64", "128")),
     "int3_block": ("CFX_INT3_BLOCK", "64", ("32", "64", "128")),
     "captured_layer": ("CFX_CAPTURED_LAYER", "0", None),
+    "attn_merge": ("CFX_ATTN_MERGE", "chain", ("chain", "once")),
 }
 _explicit: Dict[str, str] = {}
 

@@ -497,7 +497,7 @@ int    cfx_binary_rank_decompress_batch(cfx_ctx* ctx, int N, int C, int rank, in
  * sender's error-feedback update, 17-22 low-rank chain (prep, aq, aty, chol, apply, decode), 23 binary_pipe (steady-state
  * fused launch of cfx_plan_run_pipelined), 24 binary_pipe prologue / epilogue / ragged-unit launches, 25 residual2_delta,
  * 26 residual2_update, 27 absmean_compress<bits> (statistics + sign bits + in-launch finalize [+ ride-along reconstruction]),
- * 28 absmean_compress (2-bit statistics + in-launch finalize), 29 minmax_compress (int4 / int8 statistics + in-launch finalize), 30 attn_merge (cfx_attn_merge_ex's launches too). */
+ * 28 absmean_compress (2-bit statistics + in-launch finalize), 29 minmax_compress (int4 / int8 statistics + in-launch finalize), 30 attn_merge (cfx_attn_merge_ex's and cfx_attn_merge_many's launches too). */
 int         cfx_profile_enable(cfx_ctx* ctx, int capacity, unsigned kernel_mask, int stride);
 int         cfx_profile_read(cfx_ctx* ctx, int* kernel_ids, float* ms, int cap);
 const char* cfx_kernel_name(int kernel_id);
@@ -747,6 +747,33 @@ int cfx_attn_merge_wait(cfx_ctx* ctx, void* out, void* lse, const void* block_ou
 #define CFX_MERGE_FIRST 2
 int cfx_attn_merge_ex(cfx_ctx* ctx, void* out, void* lse, const void* block_out, const void* block_lse, int B, int S, int H, int D,
                       int flags, const void* wait_flag, unsigned wait_value, void* final_out, void* stream);
+
+/* ALL of a layer's blocks merged in ONE launch: the softmax-weighted combination of n blocks (1 <= n <= CFX_MERGE_MAX_BLOCKS) formed
+ * directly, not as a chain of cfx_attn_merge_ex calls - every block's output is read once, the result written once.
+ *   block_outs[i]   fp16 (bf16 with CFX_ELEM_BF16) [B][H][S][D], or [B][S][H][D] with CFX_MERGE_BSHD (all blocks alike), 16-byte aligned
+ *   block_lses[i]   fp32 [B][H][S]
+ *   out             with CFX_MERGE_OUT_F32: fp32 [B][S][H][D] - what the chain leaves in its accumulator; without: the same fp32 value
+ *                   rounded to the element type (nearest even) into a contiguous 16-bit [B][S][H][D] tensor, the layer's result
+ *   lse             fp32 [B][S][H]
+ * The two tables are HOST arrays of n device pointers, copied into the launch's arguments: nothing is allocated or written on the
+ * device besides out / lse, and the launch can be captured into a hipGraph (the graph holds the pointers).  out / lse alias no input.
+ * Arithmetic, per row (b, s, h), in fp32, every operation rounded once, none contracted:
+ *   m     = max_i lse_i
+ *   x_i   = lse_i - m                       one subtraction (0 for the maximum)
+ *   e_i   = exp(x_i)                        the fast exponential (2^(fp32(log2 e) x_i), rounded product); exactly 1 for the maximum
+ *   Z     = ((e_0 + e_1) + e_2) + ...       n - 1 additions in index order
+ *   a_d   = ((e_0 o_0d + e_1 o_1d) + ...)   each product rounded, n - 1 additions in index order
+ *   out_d = a_d / Z                         one correctly rounded DIVISION (not a reciprocal and a product)
+ *   lse   = m + logf(Z)                     one logarithm, one addition
+ * n = 1 returns the block's own values and lse exactly (e = 1, Z = 1, logf(1) = 0).  Finite inputs.
+ * `flags`: CFX_MERGE_BSHD, CFX_ELEM_BF16, CFX_MERGE_OUT_F32; CFX_MERGE_FIRST is not accepted here.  Checks, in this order: a NULL pointer -
+ * entries of the two tables included - CFX_ERR_NULL, an unknown flag bit CFX_ERR_CODEC, n outside 1 .. 16 or the shape (D % 8 == 0,
+ * D <= 512) CFX_ERR_SHAPE, 16-byte alignment of out and of every block_outs[i] CFX_ERR_ALIGN, a pending gate error CFX_ERR_GATE.  The
+ * launch reports as kernel id 30 (attn_merge) in cfx_profile_read: ONE record where the chain leaves n. */
+#define CFX_MERGE_MAX_BLOCKS 16
+#define CFX_MERGE_OUT_F32 4
+int cfx_attn_merge_many(cfx_ctx* ctx, int n, const void* const* block_outs, const void* const* block_lses,
+                        int B, int S, int H, int D, int flags, void* out, void* lse, void* stream);
 
 /* Bandwidth probe: dst[i] = src[i] over `bytes` (multiple of 16) - the achievable-HBM reference
  * against which bench.py reports roofline fractions. */
