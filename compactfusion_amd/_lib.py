@@ -24,6 +24,7 @@ MERGE_BSHD = 1           # cfx_attn_merge_ex `flags` (with ELEM_BF16: block_out 
 MERGE_FIRST = 2
 MERGE_OUT_F32 = 4        # cfx_attn_merge_many `flags` (with MERGE_BSHD, ELEM_BF16): out is fp32, not the element type
 MERGE_MAX_BLOCKS = 16
+ATTN_MAX_BLOCKS = 16     # cfx_attn_fwd_blocks: K,V blocks of one launch (its `flags`: ELEM_BF16 only)
 
 
 class CompItem(ctypes.Structure):
@@ -171,6 +172,10 @@ SYMBOLS = [
     ("cfx_attn_merge_ex", ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
     ("cfx_attn_merge_many", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
                                           + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3),
+    ("cfx_attn_fwd_blocks", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
+                                          + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint] + [ctypes.c_void_p] * 3),
+    ("cfx_attn_fwd_launches", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]),
+    ("cfx_set_attn_qtile", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
 ]
 
 # include/cfx_dev.h: exported by the DEVELOPER library only (libcfx_dev.so, -DCFX_DEV_PROBES).  Bound when - and only when - that library

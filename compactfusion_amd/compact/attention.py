@@ -5,7 +5,8 @@ The reference takes these from un-vendored third-party packages (`yunchang.ring.
 They are restated here from the published ring-attention algorithm:
     out <- out - sigmoid(lse_b - lse) * (out - out_b) ;  lse <- lse - logsigmoid(lse - lse_b)
 The attention math itself is not part of the compressed-exchange hot path; on the GPU it is PyTorch-ROCm's fused
-SDPA kernel, elsewhere an explicit fp32 softmax."""
+SDPA kernel, elsewhere an explicit fp32 softmax.  Opt-in (configure(attention="native")): `attention_blocks`, ONE native launch
+over all of a layer's K,V blocks where they lie (cfx_attn_fwd_blocks) in place of W SDPA calls and their merge."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -135,6 +136,88 @@ def _merge_many_native(block_outs, block_lses, bshd, out_dtype):
     if rc != 0:
         codecs._check(ctx, rc, "cfx_attn_merge_many")
     return out, lse
+
+
+def attention_blocks(q, ks, vs, softmax_scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The attention of q (B, Sq, H, D) over ALL the K,V blocks ks[i], vs[i] (B, Sk, H, D) - non-causal, no dropout - as if they were
+    one sequence: out (B, Sq, H, D) in q.dtype, lse fp32 as the (B, H, Sq) view of a (B, Sq, H) tensor.  Nothing is concatenated and no
+    per-block out / lse exists (include/cfx.h, cfx_attn_fwd_blocks, states the arithmetic rounding by rounding).
+    On the GPU - q and every block fp16 or bf16 alike, contiguous, 16-byte aligned, on one device, D 64 or 128, the blocks of one shape
+    that agrees with q in B, H and D - this is ONE native launch.  The launch takes at most 16 blocks: more on the native path are
+    REFUSED (ValueError), as `merge_blocks` refuses them.  Anything else (CPU tensors: the host-logic tests; other types, head dims or
+    layouts) runs the direct definition in eager fp32 torch."""
+    n = len(ks)
+    if n == 0 or n != len(vs):
+        raise ValueError(f"attention_blocks: {n} K blocks, {len(vs)} V blocks")
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    if attn_native_ok(q, ks, vs):
+        from .. import _lib
+        if n > _lib.ATTN_MAX_BLOCKS:
+            raise ValueError(f"attention_blocks: {n} blocks - the one-launch attention takes at most {_lib.ATTN_MAX_BLOCKS} "
+                             "(configure(attention='sdpa') attends to any number)")
+        return _attn_fwd_native(q, ks, vs, softmax_scale)
+    qt = q.float().transpose(1, 2)                                                            # (B, H, Sq, D)
+    s = torch.cat([torch.matmul(qt, k.float().permute(0, 2, 3, 1)) for k in ks], dim=-1) * softmax_scale
+    m = s.max(dim=-1, keepdim=True).values
+    p = torch.exp(s - m)
+    l = p.sum(dim=-1, keepdim=True)
+    out = torch.matmul(p, torch.cat([v.float().transpose(1, 2) for v in vs], dim=-2)) / l
+    lse = torch.empty((q.shape[0], q.shape[1], q.shape[2]), dtype=torch.float32, device=q.device)   # (B, Sq, H), as the launch stores it
+    lse.copy_((m + torch.log(l)).squeeze(-1).transpose(1, 2))
+    return out.transpose(1, 2).contiguous().to(q.dtype), lse.transpose(1, 2)
+
+
+def attn_native_ok(q, ks, vs) -> bool:
+    """whether `attention_blocks` takes (q, ks, vs) to the native launch (the number of blocks aside)"""
+    if not (q.is_cuda and q.dim() == 4 and q.dtype in (torch.float16, torch.bfloat16) and q.shape[-1] in (64, 128)
+            and q.is_contiguous() and q.data_ptr() % 16 == 0 and q.shape[1] > 0):
+        return False
+    k0 = ks[0]
+    if k0.dim() != 4 or k0.shape[1] <= 0 or (k0.shape[0], k0.shape[2], k0.shape[3]) != (q.shape[0], q.shape[2], q.shape[3]):
+        return False
+    return all(t.shape == k0.shape and t.dtype == q.dtype and t.device == q.device and t.is_contiguous() and t.data_ptr() % 16 == 0
+               for t in list(ks) + list(vs))
+
+
+_attn_fwd_fn = None
+
+
+def _attn_fwd_native(q, ks, vs, softmax_scale, tabs=None):
+    """the launch itself, on arguments `attn_native_ok` passed; `tabs`: the caller's two ctypes pointer tables (compact/ring.py keeps
+    a layer's), built here otherwise"""
+    global _attn_fwd_fn
+    import ctypes
+    from .. import _lib, codecs
+    n = len(ks)
+    B, Sq, H, D = q.shape
+    dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    if _attn_fwd_fn is None:
+        _attn_fwd_fn = _lib.load().cfx_attn_fwd_blocks
+    if tabs is None:
+        P = ctypes.c_void_p * n
+        tabs = P(*[t.data_ptr() for t in ks]), P(*[t.data_ptr() for t in vs])
+    out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, Sq, H), dtype=torch.float32, device=q.device)
+    ctx = codecs.context(dev)
+    rc = _attn_fwd_fn(ctx, n, q.data_ptr(), tabs[0], tabs[1], B, Sq, ks[0].shape[1], H, D, softmax_scale,
+                      _lib.ELEM_BF16 if q.dtype == torch.bfloat16 else 0, out.data_ptr(), lse.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        codecs._check(ctx, rc, "cfx_attn_fwd_blocks")
+    return out, lse.transpose(1, 2)
+
+
+def attn_fwd_launches(device=None) -> int:
+    """cfx_attn_fwd_blocks launches enqueued so far on the device's context (the launch carries no kernel id: the context counts)"""
+    import ctypes
+    from .. import _lib, codecs
+    dev = torch.cuda.current_device() if device is None else (device.index if isinstance(device, torch.device) else device)
+    n = ctypes.c_ulonglong(0)
+    ctx = codecs.context(dev)
+    rc = _lib.load().cfx_attn_fwd_launches(ctx, ctypes.byref(n))
+    if rc != 0:
+        codecs._check(ctx, rc, "cfx_attn_fwd_launches")
+    return int(n.value)
 
 
 def flag_wait(wait, device) -> None:

@@ -26,7 +26,7 @@ from .. import config as _settings
 from ..collector import collector as _collector_mod
 from ..prof import Profiler
 from . import main as cm
-from .attention import block_attention, flag_wait, merge_blocks, update_out_and_lse
+from .attention import _attn_fwd_native, attn_native_ok, block_attention, flag_wait, merge_blocks, update_out_and_lse
 from .main import compact_cache, compact_compress, compact_config, compact_decompress
 from .utils import COMPACT_COMPRESS_TYPE
 
@@ -262,6 +262,7 @@ class _SteadyLayer:
     codec and the tensor geometry stay what they were (any change falls back to the general path, which re-binds)."""
     _fast = None                 # `_fast_ok`'s answer, once asked
     _fwait = None                # cfx_flag_wait, bound at the first attn_merge="once" call of a lane form
+    _native = None               # `_native_ok`'s answer for the peers' states, once asked
 
     def __init__(self, ex, q, k, v, ctype, cfg, rank, world):
         cache = compact_cache()
@@ -359,8 +360,12 @@ class _SteadyLayer:
         configure(attn_merge="once"): no running out / lse - the blocks' results are kept and ONE launch (`merge_blocks`,
         cfx_attn_merge_many) merges them after block W-1, writing q.dtype; on the lane forms the wait the merge of block s carried is a
         stand-alone cfx_flag_wait behind block s (s < W-1), issue(s, lean) is called where it always was, and what is returned has the
-        chain's types, shapes and views."""
+        chain's types, shapes and views.
+        configure(attention="native"), where the launch takes the layer (`_native_ok`): no SDPA call and no merge at all - ONE
+        cfx_attn_fwd_blocks launch over own K,V and the peers' states where they lie (`_blocks_native`); attn_merge is ignored."""
         last = self.world - 1
+        if _settings.get("attention") == "native" and self._native_ok(q, k, v):
+            return self._blocks_native(q, k, v, softmax_scale, issue, flag, epoch)
         if _settings.get("attn_merge") == "once":
             return self._blocks_once(q, k, v, softmax_scale, sh, issue, flag, epoch)
         if self._fast_ok(q):
@@ -395,6 +400,35 @@ class _SteadyLayer:
                     wait = (flag(s + 1), epoch)
             out, lse = update_out_and_lse(out, lse, bo, bl, wait)
         return out.to(q.dtype), lse.squeeze(dim=-1).transpose(1, 2), None
+
+    def _native_ok(self, q, k, v) -> bool:
+        """Whether the one-launch attention takes this layer: the peers' states are asked once per layer (they are the arena's: their
+        addresses and shapes stand while the layer is steady), the call's own q, k, v every time."""
+        if self._native is None:
+            from .. import _lib
+            pk, pv = [kk for _, kk, _ in self._peers], [vv for _, _, vv in self._peers]
+            self._native = self.world <= _lib.ATTN_MAX_BLOCKS and attn_native_ok(q, [k] + pk, [v] + pv)
+            if self._native:
+                import ctypes
+                P = ctypes.c_void_p * self.world
+                self._ntabs = P(0, *[t.data_ptr() for t in pk]), P(0, *[t.data_ptr() for t in pv])     # entry 0: the call's own K, V
+                self._nks, self._nvs = [None] + pk, [None] + pv
+        return self._native and attn_native_ok(q, (k,), (v,))
+
+    def _blocks_native(self, q, k, v, softmax_scale, issue, flag, epoch):
+        """`_blocks` with configure(attention="native").  The launch reads every peer's state, so on the lane forms the layer's whole
+        chain is issued first - issue(s, lean) for s = 0 .. W-1, in the order the blocks would have called it - then a stand-alone
+        cfx_flag_wait on each of flag(1 .. W-1), then the launch: inside a layer the lane overlaps nothing with it."""
+        if issue is not None:
+            for s in range(self.world):
+                issue(s, True)
+            for s in range(1, self.world):
+                flag_wait((flag(s), epoch), q.device)
+        tk, tv = self._ntabs
+        tk[0], tv[0] = k.data_ptr(), v.data_ptr()
+        self._nks[0], self._nvs[0] = k, v
+        out, lse = _attn_fwd_native(q, self._nks, self._nvs, softmax_scale, self._ntabs)
+        return out, lse, None
 
     def _blocks_once(self, q, k, v, softmax_scale, sh, issue, flag, epoch):
         """`_blocks` with configure(attn_merge="once"): the lean path and the general one"""

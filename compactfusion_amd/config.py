@@ -46,6 +46,13 @@ attn_merge             CFX_ATTN_MERGE                chain | once - how a steady
                                                      results are kept and ONE launch merges them after the last block (cfx_attn_merge_many, at
                                                      most 16 blocks), the lane forms' "next peer reconstructed" waits becoming stand-alone
                                                      cfx_flag_wait launches.  The relay schedule and a layer's first (binding) call keep the chain
+attention              CFX_ATTENTION                 sdpa | native - who computes a steady layer's attention in compact_fwd: sdpa (default) = the fused SDPA
+                                                     op once per K,V block, merged as attn_merge says; native = ONE launch over all W blocks
+                                                     where they lie (cfx_attn_fwd_blocks: fp16 / bf16, head dim 64 or 128, at most 16 blocks),
+                                                     no per-block results and no merge - attn_merge is ignored; on the lane forms the layer's
+                                                     chain is issued first and the launch follows stand-alone cfx_flag_wait launches on every
+                                                     peer's flag.  The relay schedule, a layer's first (binding) call, joint tensors, causal,
+                                                     dropout and whatever the launch does not take keep the sdpa path
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process
 """
@@ -70,6 +77,7 @@ _SETTINGS = {
     "int3_block": ("CFX_INT3_BLOCK", "64", ("32", "64", "128")),
     "captured_layer": ("CFX_CAPTURED_LAYER", "0", None),
     "attn_merge": ("CFX_ATTN_MERGE", "chain", ("chain", "once")),
+    "attention": ("CFX_ATTENTION", "sdpa", ("sdpa", "native")),
 }
 _explicit: Dict[str, str] = {}
 

@@ -115,6 +115,8 @@ struct cfx_ctx {
     void* lrs_last_stream;          // the stream of the last slab-resident launch (launches of two streams must not be in flight together)
     hipEvent_t lrs_ev;
     char err[256];
+    int attn_qtile;                     // cfx_set_attn_qtile: query rows per workgroup of cfx_attn_fwd_blocks (0 = the library's choice)
+    unsigned long long attn_launches;   // cfx_attn_fwd_blocks launches enqueued on this context (cfx_attn_fwd_launches): the launch carries no kernel id
 };
 
 // what the launches of a context hand their kernels as `Probe` (developer build: the buffer cfx_dev_stamps set; product build: nothing)

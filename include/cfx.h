@@ -775,6 +775,48 @@ int cfx_attn_merge_ex(cfx_ctx* ctx, void* out, void* lse, const void* block_out,
 int cfx_attn_merge_many(cfx_ctx* ctx, int n, const void* const* block_outs, const void* const* block_lses,
                         int B, int S, int H, int D, int flags, void* out, void* lse, void* stream);
 
+/* Native ring-attention forward: the attention of a rank's queries over ALL of a layer's K,V blocks in ONE launch - non-causal, no
+ * dropout -, the blocks read where they lie through two pointer tables: no concatenation, no per-block out / lse, no merge.
+ *   q               fp16 (bf16 with CFX_ELEM_BF16: every tensor alike) [B][Sq][H][D] contiguous, 16-byte aligned; D = 64 or 128
+ *   ks[i], vs[i]    i < n, 1 <= n <= CFX_ATTN_MAX_BLOCKS: [B][Sk][H][D] contiguous, 16-byte aligned, ONE Sk for all blocks - the
+ *                   arena's (N, C) state layout with C = H D.  The keys of the blocks count as one sequence, in table order
+ *   out             [B][Sq][H][D] in the element type;  lse  fp32 [B][Sq][H] (natural logarithm), both 16-byte aligned
+ * The two tables are HOST arrays of n device pointers, copied into the launch's arguments: nothing is allocated or written on the device
+ * besides out / lse, and the launch can be captured into a hipGraph (the graph holds the pointers).  out / lse alias no input.  The
+ * launch waits for nothing: every block must be complete in stream order (cfx_flag_wait in front of it where a lane produces them).
+ * Sq and Sk are arbitrary positive numbers.  A workgroup owns 128 consecutive query rows of one (b, h) - a wave 32 - and walks the
+ * blocks in table order in tiles of 64 keys with one running (m, l, O) per row; keys past a block's end are masked.
+ * Arithmetic, per query row, every fp32 operation rounded once, none contracted; j runs over a tile's keys:
+ *   a_j   = sum_d q_d k_jd                  fp32 accumulation of the EXACT 16-bit products (v_mfma_f32_32x32x16), hardware order
+ *   t_j   = a_j * softmax_scale             one fp32 product; a masked key: t_j = -inf
+ *   m'    = max(m, max_j t_j)               updated at EVERY tile (no deferred maximum); m = -inf before the first tile
+ *   f     = exp(m - m')                     the fast exponential, 2^(fp32(log2 e) x) with the product rounded: 0 at the first tile, exactly
+ *                                           1 when the maximum stands
+ *   p_j   = exp(t_j - m')                   one subtraction, the same exponential; exactly 1 for the maximum, 0 for a masked key
+ *   l     = l * f + sum_j p_j               from the UNROUNDED p_j, fp32 additions: a lane adds its 32 keys of the tile in register order
+ *                                           (two lanes share a row and are added once, at the end)
+ *   O_d   = O_d * f + sum_j P_j v_jd        O_d * f one rounding per tile (skipped where f = 1 for a whole wave: the same value);
+ *                                           P_j = p_j rounded to the element type (nearest even), the products exact, the fp32
+ *                                           accumulation in hardware order
+ *   out_d = O_d / l                         ONE correctly rounded division, then one rounding to the element type (nearest even)
+ *   lse   = m + logf(l)
+ * n = 1, Sk = 1: p = 1, l = 1 - out is v's own bits, lse = a * softmax_scale.  Finite inputs.  Query rows past Sq are computed on zero
+ * queries and never stored.
+ * `flags`: CFX_ELEM_BF16 only.  Checks, in this order: a NULL pointer - entries of the two tables included - CFX_ERR_NULL; an unknown
+ * flag bit CFX_ERR_CODEC; n outside 1 .. 16, a non-positive size, D other than 64 or 128, more workgroups than a launch takes, a scale
+ * that is not finite and positive CFX_ERR_SHAPE; q, out, lse or a block not 16-byte aligned CFX_ERR_ALIGN; a pending gate error
+ * CFX_ERR_GATE.  Each returns before anything is launched.
+ * The 32-bit kernel-id mask of cfx_profile_enable is full: the launch carries NO kernel id and is not recorded there.  The context
+ * counts the launches it enqueued instead; cfx_attn_fwd_launches reads the count (a captured launch counts once, its replays not). */
+#define CFX_ATTN_MAX_BLOCKS 16
+int cfx_attn_fwd_blocks(cfx_ctx* ctx, int n, const void* q, const void* const* ks, const void* const* vs, int B, int Sq, int Sk, int H, int D,
+                        float softmax_scale, unsigned flags, void* out, void* lse, void* stream);
+int cfx_attn_fwd_launches(cfx_ctx* ctx, unsigned long long* n);
+/* Query rows a workgroup of cfx_attn_fwd_blocks owns: 64, 128 or 256 (2, 4 or 8 waves), 0 = the library's choice (128: measured best on
+ * the FLUX shard).  The result is the same function of the inputs whatever the tile; anything else is CFX_ERR_SHAPE.  For
+ * measurement (tools/attn_rows.py). */
+int cfx_set_attn_qtile(cfx_ctx* ctx, int rows);
+
 /* Bandwidth probe: dst[i] = src[i] over `bytes` (multiple of 16) - the achievable-HBM reference
  * against which bench.py reports roofline fractions. */
 int cfx_copy_probe(cfx_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream);
