@@ -1534,27 +1534,7 @@ static bool gated_one_launch(cfx_ctx* ctx, int codec, int C, int CB) {
 // word must never carry a tag a later launch expects, so it starts zeroed and only ever takes this context's tags, handed out in
 // sequence (24 bits, never 0; when they wrap the arenas are zeroed again, in stream order).  Returns the launch's tag, 0 on failure.
 static unsigned abs_arena_for(cfx_ctx* ctx, unsigned ring, void* stream, size_t need_bytes, u64** arena) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!ctx->mml_arena_owned[ring] || ctx->mml_arena_owner[ring] != stream) {
-        // the ring - and with it its arenas - changed hands: whatever its previous owner still has in flight reads them.  Rare; wait for it
-        if (ctx->mml_arena_owned[ring]) (void)hipDeviceSynchronize();
-        ctx->mml_arena_owner[ring] = stream;
-        ctx->mml_arena_owned[ring] = true;
-    }
-    if (ctx->abs_arena_bytes[ring] < need_bytes) {
-        if (ctx->abs_arena[ring]) (void)hipFree(ctx->abs_arena[ring]);      // (synchronises the device: no launch still reads it)
-        ctx->abs_arena[ring] = nullptr;
-        ctx->abs_arena_bytes[ring] = 0;
-        const size_t cap = (std::max(need_bytes, (size_t)2 << 20) + 4095) & ~(size_t)4095;
-        void* m = nullptr;
-        if (hipMalloc(&m, cap) != hipSuccess || hipMemsetAsync(m, 0, cap, s) != hipSuccess) {
-            (void)hipGetLastError();
-            if (m) (void)hipFree(m);
-            return 0;
-        }
-        ctx->abs_arena[ring] = (u64*)m;
-        ctx->abs_arena_bytes[ring] = cap;
-    }
+    if (!ring_arena_reserve(ctx, ring, stream, &ctx->abs_arena[ring], &ctx->abs_arena_bytes[ring], need_bytes, (size_t)2 << 20)) return 0;
     unsigned tag = ++ctx->abs_seq & 0xFFFFFFu;
     if (tag == 0) {
         // 16.7 million launches later: a word a smaller layout has not touched since could carry a tag again - start over
@@ -1650,10 +1630,9 @@ static int absmean_compress2(CompressCall& cc) {
 int cfx_i_absmean_compress(CompressCall& cc) {
     if (cc.second) return absmean_compress2(cc);
     cfx_ctx* ctx = cc.ctx;
-    const int codec = cc.codec, N = cc.N, C = cc.C, param = cc.param, flags = cc.flags, batch = cc.batch, n_ride = cc.n_ride, CB = cc.CB;
+    const int codec = cc.codec, N = cc.N, C = cc.C, flags = cc.flags, batch = cc.batch, n_ride = cc.n_ride, CB = cc.CB;
     int n_gated = cc.n_gated;
     const cfx_comp_item* items = cc.items;
-    const cfx_decomp_item* gated = cc.gated;
     void* stream = cc.stream;
     hipStream_t s = (hipStream_t)stream;
     CfxXGate* xg = cc.xg;
@@ -1661,18 +1640,16 @@ int cfx_i_absmean_compress(CompressCall& cc) {
     BatchD rd = cc.rd, gd = cc.gd;
     u64* ws = cc.ws;
     const size_t wstride = cc.wstride;
-    const bool upd = cc.upd, capturing = cc.capturing, bf16 = cc.bf16;
-    (void)param; (void)n_ride; (void)items; (void)gated; (void)rd; (void)ws; (void)wstride; (void)upd; (void)capturing; (void)xg; (void)gd;
+    const bool upd = cc.upd, bf16 = cc.bf16;
     const bool fused = cc.fused;
     unsigned* tick = cc.tick;
     const unsigned slot = cc.slot;
     const int stream_cus = cc.stream_cus, R = cc.R, P = cc.P;
-    (void)tick; (void)slot;
     // one launch only for explicit gated items: folding the error-feedback update of a PLAIN compress call into the launch the same
     // way was measured slower (K,V of the FLUX shard: 20.8 vs 19.2 us 1-bit, 19.9 vs 18.6 us 2-bit) - the gate hop and the write tail
     // cost more than the kernel boundary they replace when only two tensors wait behind the gate
     // (2-bit: the tile stays in registers - exactly one trip of the row loop; 1-bit: any whole number of trips)
-    bool one_launch = n_gated && !capturing && gated_one_launch(ctx, codec, C, CB) &&
+    bool one_launch = n_gated && !cc.capturing && gated_one_launch(ctx, codec, C, CB) &&
                       (R == FUSED_NW * 4 || (codec == CFX_CODEC_BINARY && R % (FUSED_NW * 4) == 0));
     if (one_launch && codec == CFX_CODEC_INT2) {
         // the 2-bit layer launch needs every statistics workgroup CO-RESIDENT (each waits at gate 1 for all the others' partial sums
@@ -1715,7 +1692,6 @@ int cfx_i_absmean_compress(CompressCall& cc) {
     const dim3 grid(CB, P, batch);
     const int Rq = auto_rows(ctx, N, C, batch, true);       // apply passes: same tile map as the (unfused) statistics pass
     const dim3 gridq(CB, (N + Rq - 1) / Rq, batch);
-    (void)gridq;
     const int per_byte = codec == CFX_CODEC_BINARY ? 8 : 4;
     if (one_launch && codec == CFX_CODEC_INT2) {
         Int2LayerArgs a;

@@ -3,6 +3,7 @@
 // Not part of the ABI.
 #ifndef CFX_HOST_H
 #define CFX_HOST_H
+#include <algorithm>
 #include "cfx_device.h"
 
 // One compress call after validation: what cfx_api.hip's compress_impl has checked and packed, handed to the family that launches it.
@@ -66,6 +67,34 @@ struct LocalLayerArgs;
 CFX_HIDDEN dim3 cfx_i_local_grid(int N, int C, int batch);
 CFX_HIDDEN int cfx_i_local_layer(CompressCall& cc, LocalLayerArgs& a);
 CFX_HIDDEN int cfx_i_local_tail(CompressCall& cc, const char* what);
+// A ring's arena of TAGGED words (the min/max and the abs-mean layer launches: `arena` / `bytes` are the family's fields of the context for
+// this ring), at least `need` bytes for a launch on `stream`.  Context-owned because a stale word must never carry a tag a later launch
+// expects: it starts zeroed and only ever takes this context's tags.  Returns the arena, NULL when it cannot be allocated.
+static inline u64* ring_arena_reserve(cfx_ctx* ctx, unsigned ring, void* stream, u64** arena, size_t* bytes, size_t need, size_t min_cap) {
+    if (!ctx->mml_arena_owned[ring] || ctx->mml_arena_owner[ring] != stream) {
+        // the ring - and with it its arenas - changed hands (more than CFX_RING_STREAMS streams issue compress launches): whatever its
+        // previous owner still has in flight reads them.  Rare by construction; wait for it
+        if (ctx->mml_arena_owned[ring]) (void)hipDeviceSynchronize();
+        ctx->mml_arena_owner[ring] = stream;
+        ctx->mml_arena_owned[ring] = true;
+    }
+    if (*bytes < need) {
+        if (*arena) (void)hipFree(*arena);      // (synchronises the device: no launch still reads it)
+        *arena = nullptr;
+        *bytes = 0;
+        const size_t cap = (std::max(need, min_cap) + 4095) & ~(size_t)4095;
+        void* m = nullptr;
+        // (zeroed IN the launch stream: a plain hipMemset runs on the NULL stream, which a non-blocking stream does not wait for)
+        if (hipMalloc(&m, cap) != hipSuccess || hipMemsetAsync(m, 0, cap, (hipStream_t)stream) != hipSuccess) {
+            (void)hipGetLastError();
+            if (m) (void)hipFree(m);
+            return nullptr;
+        }
+        *arena = (u64*)m;
+        *bytes = cap;
+    }
+    return *arena;
+}
 // (short names the family files were written with)
 #define auto_rows cfx_i_auto_rows
 #define fused_rows cfx_i_fused_rows

@@ -548,7 +548,7 @@ __device__ __forceinline__ void lr_apply_body(const LrItem& it, int bx, int rows
 // compress_quantize.py:552-573: per column min / max over the rows, scale = fp16(fp16(max - min) / 15.000001), codes
 // round((x - min) / scale) clamped to 0 .. 15, two ROWS per byte) and - want_dq - the factors the receiver will see
 // (q * scale + min, two fp16 roundings: compress_quantize.py:626-636) for the error-feedback decode.  The arithmetic of
-// k_minmax_compress / k_int4_quant / k_int4_dequant applied to a rows x r matrix (bit-identical: tests), without their nine launches and
+// k_minmax_compress / k_minmax_quant<2> / k_minmax_dequant<2> applied to a rows x r matrix (bit-identical: tests), without their nine launches and
 // copies for matrices of 17 K and 98 K elements.  grid.x: blocks [0, nsu) = U (N x r) in row shares (one for a shard of up to ~1000 rows),
 // the next LRQ_VS = V^T (C x r) in row shares; every block finds the column statistics of its whole matrix itself (32 columns: cheaper
 // than waiting for each other).
@@ -649,7 +649,7 @@ __global__ __launch_bounds__(1024) void k_lr_q4(LrQ4Batch b, int N, int C, int r
 }
 
 // The receiver's side of k_lr_q4: both int4 factors of every tensor back to fp16 (q * scale + min, two roundings:
-// compress_quantize.py:626-636; the arithmetic of k_int4_dequant) in one launch.  Sections may start at addresses that are only 8-byte
+// compress_quantize.py:626-636; the arithmetic of k_minmax_dequant<2>) in one launch.  Sections may start at addresses that are only 8-byte
 // aligned: the codes are read 8 bytes at a time.  grid.x as k_lr_q4's.
 struct LrDq4 { const unsigned char* secU; const unsigned char* secV; h16* Uq; h16* Vq; };
 struct LrDq4Batch { LrDq4 it[LR_MAXB]; };

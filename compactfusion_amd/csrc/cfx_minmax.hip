@@ -96,23 +96,42 @@ __device__ __forceinline__ h16 hdiv_r(h16 a, float bf, float rb) {
 }
 __device__ __forceinline__ bool hisnan(h16 a) { return a != a; }
 
-// int4 : scale = fp16(fp16(max-min)/15.000001f), min                              compress_quantize.py:556-558
-// int2 min/max : scale = fp16(fp16(max-min)/3.000001f), min                       compress_quantize.py:402-404
-// int8 : scale = fp16(fp16(max-min)/255.0f), zp = clamp(-128 - round(min/scale)) -> int16          :455-463
-__device__ __forceinline__ void minmax_write_scales(const cfx_comp_item& it, int N, int C, int codec, int c, h16 mn, h16 mx) {
+// The family's members by RPC, the rows one code row (C bytes) of the packet holds: 1 = int8, 2 = int4 (16 levels), 4 = INT2_MINMAX (4 levels)
+__host__ __device__ constexpr int mml_rpc(int codec) { return codec == CFX_CODEC_INT4 ? 2 : codec == CFX_CODEC_INT2_MINMAX ? 4 : 1; }
+
+// One channel's code of delta d as an unsigned byte field, given the channel's mz (min; int8: zero point), bf = (float)scale and
+// rb = v_rcp_f32(bf) - the only statement of the code arithmetic, fp16 after each operation of the reference:
+//   int4, INT2_MINMAX : clamp(round((d - min) / scale), 0, 2^(8/RPC) - 1)         compress_quantize.py:560-564, :406-410
+//   int8              : clamp(round(d / scale + zp), -128, 127), as a byte                               :465-467
+// NaN gives 0 (fmax / fmin return their other operand; int8's lower bound is not 0, so it tests).
+template <int RPC>
+__device__ __forceinline__ unsigned minmax_code(h16 d, h16 mz, float bf, float rb) {
+    constexpr int BITS = 8 / RPC;
+    const h16 q = hdiv_r(RPC > 1 ? d - mz : d, bf, rb);
+    h16 v = hrint(RPC > 1 ? q : q + mz);
+    if (RPC > 1) {
+        v = __builtin_fmaxf16(v, (h16)0);
+        v = __builtin_fminf16(v, (h16)(float)((1 << BITS) - 1));
+        return (unsigned)(unsigned short)v & ((1u << BITS) - 1u);
+    }
+    if (hisnan(v)) v = (h16)0;
+    v = __builtin_fmaxf16(v, (h16)-128.0f);
+    v = __builtin_fminf16(v, (h16)127.0f);
+    return (unsigned char)(signed char)(short)v;
+}
+
+// scale and second word of one channel from its {min, max} - the only statement of the scale arithmetic:
+//   int4         : scale = fp16(fp16(max-min) / levels), min, levels just above 15              compress_quantize.py:556-558
+//   INT2_MINMAX  : the same with levels just above 3                                                          :402-404
+//   int8         : levels just above 255; zp = clamp(-128 - round(min/scale)) -> int16                        :455-463
+template <int RPC>
+__device__ __forceinline__ void minmax_scale_of(h16 mn, h16 mx, h16& scale, u16& second) {
     const h16 rng = mx - mn;
-    if (codec == CFX_CODEC_INT4) {
-        h16* S = (h16*)((char*)it.packet + (size_t)(N / 2) * C);
-        S[c] = (h16)((float)rng / 15.000001f);
-        S[C + c] = mn;
-    } else if (codec == CFX_CODEC_INT2_MINMAX) {
-        h16* S = (h16*)((char*)it.packet + (size_t)(N / 4) * C);
-        S[c] = (h16)((float)rng / 3.000001f);
-        S[C + c] = mn;
+    if (RPC > 1) {
+        scale = (h16)((float)rng / (RPC == 2 ? 15.000001f : 3.000001f));
+        second = hbits(mn);
     } else {
-        h16* S = (h16*)((char*)it.packet + (size_t)N * C);
-        short* Z = (short*)(S + C);
-        const h16 scale = (h16)((float)rng / 255.000001f);
+        scale = (h16)((float)rng / 255.000001f);
         const h16 r = hrint(hdiv(mn, scale));
         h16 z = (h16)-128.0f - r;
         short zi;
@@ -122,13 +141,25 @@ __device__ __forceinline__ void minmax_write_scales(const cfx_comp_item& it, int
             z = z > (h16)127.0f ? (h16)127.0f : z;
             zi = (short)(float)z;
         }
-        S[c] = scale;
-        Z[c] = zi;
+        second = (u16)zi;
     }
 }
+// ... into the packet, behind its N / RPC code rows: [C] scales, then [C] mins (int4, INT2_MINMAX) or int16 zero points (int8)
+__device__ __forceinline__ void minmax_write_scales(const cfx_comp_item& it, int N, int C, int codec, int c, h16 mn, h16 mx) {
+    const int rpc = mml_rpc(codec);
+    h16 scale;
+    u16 second;
+    switch (rpc) {
+    case 2: minmax_scale_of<2>(mn, mx, scale, second); break;
+    case 4: minmax_scale_of<4>(mn, mx, scale, second); break;
+    default: minmax_scale_of<1>(mn, mx, scale, second);
+    }
+    u16* S = (u16*)((char*)it.packet + (size_t)(N >> (rpc >> 1)) * C);      // (N / rpc code rows)
+    S[c] = hbits(scale);
+    S[C + c] = second;
+}
 
-// finalize int4 : scale = fp16(fp16(max-min)/15.000001f), min                     compress_quantize.py:556-558
-//          int8 : scale = fp16(fp16(max-min)/255.0f), zp = clamp(-128 - round(min/scale)) -> int16   :455-463
+// finalize: the P partials of a channel -> its scales in the packet (minmax_scale_of)
 __global__ __launch_bounds__(1024) void k_minmax_finalize(BatchC batch, int N, int C, int P, int codec, const u64* ws, size_t ws_stride) {
     const cfx_comp_item it = batch.it[blockIdx.y];
     const unsigned* part = (const unsigned*)(ws + (size_t)blockIdx.y * ws_stride);
@@ -210,7 +241,7 @@ __global__ __launch_bounds__(NTHR) void k_minmax_compress(BatchC batch, int N, i
 //      write-through -> ticket of the column block; the block's last arriver reduces the P partials, writes scale / min (int4, INT2_MINMAX) or scale /
 //      zero point (int8) into the packet (compress_quantize.py:452-463, :552-558) and raises the block's COLUMN GATE.  The scales of a
 //      tile depend on its column block only (there is no tensor-wide statistic), so a tile waits for the P tiles of its own block, not
-//      for the launch.  Then: codes from registers (arithmetic of k_int4_quant / k_int8_quant / k_int2mm_quant), published as 16-byte write-through
+//      for the launch.  Then: codes from registers (minmax_code, the arithmetic of k_minmax_quant), published as 16-byte write-through
 //      stores through an LDS transpose, one arrival on the codes gate, error-feedback state last (nobody waits for it).
 //   D  tile (up to 112 rows x 512 channels; INT2_MINMAX: up to 128, whole row quads per wave - MML_KC / MML_KC4): state rows into registers, wait for the gate (the launch's own codes gate, or the external word an
 //      exchange stream sets once the peers' packets have arrived), codes + scales through L2-bypassing loads, finish from registers.
@@ -220,8 +251,6 @@ __global__ __launch_bounds__(NTHR) void k_minmax_compress(BatchC batch, int N, i
 #define MML_NW FUSED_NW
 #define MML_KC 14              // rows of a D tile a wave holds in registers (int4: 7 row pairs)
 #define MML_KC4 16             // ... of the 4-level codec: 4 row quads (14 is no multiple of 4; 16 state rows are 64 registers, within the 128 the S tile needs anyway)
-// The family's members by RPC, the rows one code row (C bytes) of the packet holds: 1 = int8, 2 = int4 (16 levels), 4 = INT2_MINMAX (4 levels)
-__host__ __device__ constexpr int mml_rpc(int codec) { return codec == CFX_CODEC_INT4 ? 2 : codec == CFX_CODEC_INT2_MINMAX ? 4 : 1; }
 __host__ __device__ constexpr int mml_kc(int rpc) { return rpc == 4 ? MML_KC4 : MML_KC; }
 #define MML_MAX_P 64           // row tiles per column block (one poll load per lane of a wave)
 #define MML_MAX_P_TALL 128     // ... of the tall form (two poll loads per lane)
@@ -250,7 +279,9 @@ struct MinMaxLayerArgs {
     Probe probe;                      // developer build: 16 words per workgroup (100 MHz wall clock per phase; word 7: 1 = S tile, 4 = D tile)
 };
 #define MML_STAMP(i) st.at(i)
-// received values of 8 channels of row h of a code row (int8: h = 0): k_int8_dequant / k_int4_dequant / k_int2mm_dequant arithmetic
+// received values of 8 channels of row h of a code row (int8: h = 0) - the only statement of the receiver's arithmetic: q * scale + min
+// (two roundings; contraction is off), int8 (q - zp) * scale (compress_quantize.py:626-636, :424, :482).  The code goes through an
+// integer: rint(-0.3) = -0 must dequantise as +0
 template <int RPC>
 __device__ __forceinline__ h16x8 minmax_recv(u64 codes, int h, h16x8 sc, h16x8 mz) {
     constexpr int BITS = 8 / RPC;
@@ -281,27 +312,6 @@ __device__ __forceinline__ void minmax_ld_scales(const unsigned char* pk, int N,
         const u16x8 zb = __builtin_bit_cast(u16x8, ld8_pub(S + C + cc, remote));
 #pragma unroll
         for (int i = 0; i < 8; ++i) mz[i] = (h16)(float)(short)zb[i];
-    }
-}
-// scale and min (int4, 4-level) / scale and zero point (int8) of one channel from its {min, max}: compress_quantize.py:556-558 / :402-404 / :455-463
-template <int RPC>
-__device__ __forceinline__ void minmax_scale_of(h16 mn, h16 mx, h16& scale, u16& second) {
-    const h16 rng = mx - mn;
-    if (RPC > 1) {
-        scale = (h16)((float)rng / (RPC == 2 ? 15.000001f : 3.000001f));
-        second = hbits(mn);
-    } else {
-        scale = (h16)((float)rng / 255.000001f);
-        const h16 r = hrint(hdiv(mn, scale));
-        h16 z = (h16)-128.0f - r;
-        short zi;
-        if (hisnan(z)) zi = 0;
-        else {
-            z = z < (h16)-128.0f ? (h16)-128.0f : z;
-            z = z > (h16)127.0f ? (h16)127.0f : z;
-            zi = (short)(float)z;
-        }
-        second = (u16)zi;
     }
 }
 #ifndef MML_POLL_SLEEP
@@ -535,8 +545,8 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
     // ---- own tile: codes from registers ----
     u64* stage = &sm[0][0] + (size_t)t.w * CR * 64;         // this wave's CR code rows x 64 lanes x 8 bytes (same wave writes and reads: in order)
     {
-        // codes exactly as k_int4_quant / k_int2mm_quant / k_int8_quant compute them, channel by channel: the division by the channel's scale as
-        // hdiv_r with one reciprocal per channel - this loop is the kernel's instruction count (tall tensors: it ran at the VALU's pace)
+        // codes (minmax_code, as k_minmax_quant), channel by channel: one reciprocal of the scale per channel - this loop is the kernel's
+        // instruction count (tall tensors: it ran at the VALU's pace)
         u64 cj[CR];
 #pragma unroll
         for (int j = 0; j < CR; ++j) cj[j] = 0;
@@ -544,25 +554,9 @@ __device__ __forceinline__ void minmax_layer_s_tile(const cfx_comp_item& it, con
         for (int i = 0; i < 8; ++i) {
             const float bf = (float)sc[i], rb = __builtin_amdgcn_rcpf(bf);
 #pragma unroll
-            for (int j = 0; j < CR; ++j) {
-                if (AFFINE) {
+            for (int j = 0; j < CR; ++j)
 #pragma unroll
-                    for (int h = 0; h < RPC; ++h) {
-                        const h16 d = dk[RPC * j + h][i];
-                        h16 v = hrint(hdiv_r(d - mz[i], bf, rb));
-                        v = __builtin_fmaxf16(v, (h16)0);              // (NaN -> 0, as k_int4_quant's explicit test)
-                        v = __builtin_fminf16(v, (h16)(float)((1 << BITS) - 1));
-                        cj[j] |= (u64)((unsigned)(unsigned short)v & ((1u << BITS) - 1u)) << (8 * i + BITS * h);
-                    }
-                } else {
-                    const h16 d = dk[j][i];
-                    h16 v = hrint(hdiv_r(d, bf, rb) + mz[i]);
-                    if (hisnan(v)) v = (h16)0;
-                    v = __builtin_fmaxf16(v, (h16)-128.0f);
-                    v = __builtin_fminf16(v, (h16)127.0f);
-                    cj[j] |= (u64)(unsigned char)(signed char)(short)v << (8 * i);
-                }
-            }
+                for (int h = 0; h < RPC; ++h) cj[j] |= (u64)minmax_code<RPC>(dk[RPC * j + h][i], mz[i], bf, rb) << (8 * i + BITS * h);
         }
 #pragma unroll
         for (int j = 0; j < CR; ++j) stage[j * 64 + t.lane] = cj[j];   // (kept there for the error-feedback pass too: nothing else uses the LDS afterwards)
@@ -689,7 +683,8 @@ __device__ __forceinline__ void minmax_layer_d_tile(const cfx_decomp_item& it, c
     }
 }
 
-// one body for the family (RPC = rows per code row); the kernels below are its instantiations
+// one body for the family (RPC = rows per code row).  A function of its own under the kernel: written into the kernel it compiles to a few
+// instructions more in every instantiation, and the 4-level launch measured 0.1 us slower
 template <int RPC, int RW>
 __device__ __forceinline__ void minmax_layer_body(BatchC batch, BatchD gated, MinMaxLayerArgs a, u64 (*sm)[TILE_C], u32x4* park) {
     int b = blockIdx.x;
@@ -714,331 +709,145 @@ __device__ __forceinline__ void minmax_layer_body(BatchC batch, BatchD gated, Mi
     minmax_layer_d_tile<RPC>(gated.it[item], a, item, rem - ty * a.CB, ty);
 }
 
-template <bool INT4, int RW>
+template <int RPC, int RW>
 __global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer(BatchC batch, BatchD gated, MinMaxLayerArgs a) {
     __shared__ u64 sm[MML_NW][TILE_C];
     __shared__ u32x4 park[RW > 4 ? MML_PARK * FUSED_NT : 1];           // RW = 8: 32 KB more, still two workgroups a CU
-    minmax_layer_body<INT4 ? 2 : 1, RW>(batch, gated, a, sm, park);
-}
-// the 4-level codec (INT2_MINMAX): four rows per code row, D tiles of up to 128 rows (MML_KC4)
-template <int RW>
-__global__ __launch_bounds__(FUSED_NT, 4) void k_minmax_layer4(BatchC batch, BatchD gated, MinMaxLayerArgs a) {
-    __shared__ u64 sm[MML_NW][TILE_C];
-    __shared__ u32x4 park[RW > 4 ? MML_PARK * FUSED_NT : 1];
-    minmax_layer_body<4, RW>(batch, gated, a, sm, park);
+    minmax_layer_body<RPC, RW>(batch, gated, a, sm, park);
 }
 
-// int8 quantise (+EF)      compress_quantize.py:465-467 ; EF = dequantize_int8 :482 + main.py:232
-__global__ __launch_bounds__(NTHR) void k_int8_quant(BatchC batch, int N, int C, int R, int flags) {
-    const cfx_comp_item it = batch.it[blockIdx.z];
-    const TileCoord t = tile_coord(N, C, R);
-    signed char* q = (signed char*)it.packet;
-    const h16* S = (const h16*)(q + (size_t)N * C);
-    const short* Z = (const short*)(S + C);
-    const h16* x = (const h16*)it.x;
-    const h16* base = (const h16*)it.base;
-    h16* nb = (h16*)it.new_base;
-    const bool upd = (flags & CFX_FLAG_UPDATE_CACHE) && nb;
-    const bool ef = !(flags & CFX_FLAG_NO_EF);
-    h16x8 sc = (h16x8)(h16)1.0f, zp = (h16x8)(h16)0;
-    if (t.act) {
+// ---------------------------------------------------------------------------------------------------
+// The stand-alone quantiser and dequantiser (tall tensors, captured streams, the unfused forms).  A wave step takes U code rows = U x RPC
+// tensor rows, because the packet holds RPC rows per byte along N: byte[k][c] = q[RPC k][c] | q[RPC k + 1][c] << BITS | ...
+// (compress_quantize.py:566-573 for int4; the reference has no packing for the 4-level codec).  R (rows per tile) is a multiple of RPC,
+// so no code row straddles a tile; code row index space = rows / RPC.
+// ---------------------------------------------------------------------------------------------------
+// scale vectors of a lane's 8 channels out of the packet an EARLIER launch finished; int8: zp as fp16 values.  Inactive lanes: 1 and 0
+template <int RPC>
+__device__ __forceinline__ void minmax_ld_scales_own(const unsigned char* pk, int N, int C, const TileCoord& t, h16x8& sc, h16x8& mz) {
+    const h16* S = (const h16*)(pk + (size_t)(N / RPC) * C);
+    sc = (h16x8)(h16)1.0f; mz = (h16x8)(h16)0;
+    if (!t.act) return;
+    if (RPC > 1) {
+        const bool al16 = ((((uintptr_t)S) | ((uintptr_t)(S + C))) & 15) == 0;
+        sc = ld8_tail(S + t.c, al16);
+        mz = ld8_tail(S + C + t.c, al16);
+    } else {
+        const short* Z = (const short*)(S + C);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { sc[i] = S[t.c + i]; zp[i] = (h16)(float)Z[t.c + i]; }
-    }
-    float scf[8], scr[8];                                    // the channel's scale and its reciprocal: hdiv_r
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { scf[i] = (float)sc[i]; scr[i] = __builtin_amdgcn_rcpf(scf[i]); }
-    for (int r = t.r0 + t.w; r < t.r1; r += WAVES * UNROLL) {
-        h16x8 xv[UNROLL], bv[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const int rr = r + WAVES * j;
-            xv[j] = (h16x8)(h16)0; bv[j] = (h16x8)(h16)0;
-            if (rr < t.r1 && t.act) {
-                xv[j] = ld8nt(x + (size_t)rr * C + t.c);
-                if (base) bv[j] = ld8nt(base + (size_t)rr * C + t.c);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const int rr = r + WAVES * j;
-            if (rr < t.r1 && t.act) {
-                const h16x8 d = xv[j] - bv[j];
-                u64 outb = 0;
-                h16x8 qh;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    h16 v = hrint(hdiv_r(d[i], scf[i], scr[i]) + zp[i]);   // round(x/scale + zp), fp16 after each op
-                    if (hisnan(v)) v = (h16)0;
-                    v = v < (h16)-128.0f ? (h16)-128.0f : v;
-                    v = v > (h16)127.0f ? (h16)127.0f : v;
-                    const int qi = (int)(float)v;
-                    qh[i] = (h16)(float)qi;                                 // via int: rint(-0.3) = -0 must dequantise as +0
-                    outb |= (u64)(unsigned char)(signed char)qi << (8 * i);
-                }
-                *reinterpret_cast<u64*>(q + (size_t)rr * C + t.c) = outb;
-                if (upd) {
-                    h16x8 o;
-                    if (ef) {
-                        const h16x8 recv = (qh - zp) * sc;                // (q - zp) * scale
-                        o = base ? (bv[j] + recv) : recv;
-                    } else o = xv[j];
-                    st8nt(nb + (size_t)rr * C + t.c, o);
-                }
-            }
-        }
+        for (int i = 0; i < 8; ++i) { sc[i] = S[t.c + i]; mz[i] = (h16)(float)Z[t.c + i]; }
     }
 }
 
-__global__ __launch_bounds__(NTHR) void k_int8_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
-    // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
-    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
-    const cfx_decomp_item it = batch.it[blockIdx.z];
-    const TileCoord t = tile_coord(N, C, R);
-    const signed char* q = (const signed char*)it.packet;
-    const h16* S = (const h16*)(q + (size_t)N * C);
-    const short* Z = (const short*)(S + C);
-    const h16* base = (const h16*)it.base;
-    h16* out = (h16*)it.recon;
-    h16x8 sc = (h16x8)(h16)1.0f, zp = (h16x8)(h16)0;
-    if (t.act) {
+// f(0) .. f(N - 1), the loop over the RPC rows of a code row - but no loop where N is 1 (int8): the compiler moves a non-temporal store out
+// of a loop of ONE trip as a plain store, which cost the int8 dequantiser 8 % (tests/test_resource_usage.py reads the flag in the assembly)
+template <int N, class F>
+__device__ __forceinline__ void unrolled(F&& f) {
+    if constexpr (N == 1) f(0);
+    else {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { sc[i] = S[t.c + i]; zp[i] = (h16)(float)Z[t.c + i]; }
-    }
-    for (int r = t.r0 + t.w; r < t.r1; r += WAVES * UNROLL) {
-        h16x8 bv[UNROLL];
-        u64 qb[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const int rr = r + WAVES * j;
-            bv[j] = (h16x8)(h16)0; qb[j] = 0;
-            if (rr < t.r1 && t.act) {
-                if (base) bv[j] = ld8nt(base + (size_t)rr * C + t.c);
-                qb[j] = *reinterpret_cast<const u64*>(q + (size_t)rr * C + t.c);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const int rr = r + WAVES * j;
-            if (rr < t.r1 && t.act) {
-                h16x8 qh;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) qh[i] = (h16)(float)(int)(signed char)(qb[j] >> (8 * i));
-                const h16x8 recv = (qh - zp) * sc;
-                st8nt(out + (size_t)rr * C + t.c, base ? (bv[j] + recv) : recv);
-            }
-        }
+        for (int h = 0; h < N; ++h) f(h);
     }
 }
 
-// int4 quantise (+EF): one wave step handles the row PAIR (2k, 2k+1) because the reference packs two rows per
-// byte along N (compress_quantize.py:566-573): byte[k][c] = q[2k][c] | q[2k+1][c] << 4.
-// R (rows per tile) is even; pair index space = rows/2.
-__global__ __launch_bounds__(NTHR) void k_int4_quant(BatchC batch, int N, int C, int R, int flags) {
+// quantise (+EF): codes = minmax_code; EF = the receiver's value of those codes (minmax_recv) + main.py:232
+template <int RPC>
+__global__ __launch_bounds__(NTHR) void k_minmax_quant(BatchC batch, int N, int C, int R, int flags) {
+    constexpr int U = RPC == 1 ? UNROLL : 1, BITS = 8 / RPC;
     const cfx_comp_item it = batch.it[blockIdx.z];
     const TileCoord t = tile_coord(N, C, R);
     unsigned char* q = (unsigned char*)it.packet;
-    const h16* S = (const h16*)(q + (size_t)(N / 2) * C);
-    const h16* M = S + C;
     const h16* x = (const h16*)it.x;
     const h16* base = (const h16*)it.base;
     h16* nb = (h16*)it.new_base;
     const bool upd = (flags & CFX_FLAG_UPDATE_CACHE) && nb;
     const bool ef = !(flags & CFX_FLAG_NO_EF);
-    const bool al16 = ((((uintptr_t)S) | ((uintptr_t)M)) & 15) == 0;
-    h16x8 sc = (h16x8)(h16)1.0f, mn = (h16x8)(h16)0;
-    if (t.act) { sc = ld8_tail(S + t.c, al16); mn = ld8_tail(M + t.c, al16); }
+    h16x8 sc, mz;
+    minmax_ld_scales_own<RPC>(q, N, C, t, sc, mz);
     float scf[8], scr[8];                                    // the channel's scale and its reciprocal: hdiv_r
 #pragma unroll
     for (int i = 0; i < 8; ++i) { scf[i] = (float)sc[i]; scr[i] = __builtin_amdgcn_rcpf(scf[i]); }
-    const int k0 = t.r0 >> 1, k1 = t.r1 >> 1;
-    constexpr int U2 = 1;   // one row PAIR per wave step
-    for (int k = k0 + t.w; k < k1; k += WAVES * U2) {
-        h16x8 xv[U2][2], bv[U2][2];
+    const int k1 = t.r1 / RPC;
+    for (int k = t.r0 / RPC + t.w; k < k1; k += WAVES * U) {
+        if (!t.act) continue;                               // the bounds guard of every access below, once per step: see k_minmax_dequant
+        h16x8 xv[U][RPC], bv[U][RPC];
 #pragma unroll
-        for (int j = 0; j < U2; ++j) {
+        for (int j = 0; j < U; ++j) {
             const int kk = k + WAVES * j;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < RPC; ++h) {
                 xv[j][h] = (h16x8)(h16)0; bv[j][h] = (h16x8)(h16)0;
-                if (kk < k1 && t.act) {
-                    xv[j][h] = ld8nt(x + (size_t)(2 * kk + h) * C + t.c);
-                    if (base) bv[j][h] = ld8nt(base + (size_t)(2 * kk + h) * C + t.c);
+                if (kk < k1) {
+                    xv[j][h] = ld8nt(x + (size_t)(RPC * kk + h) * C + t.c);
+                    if (base) bv[j][h] = ld8nt(base + (size_t)(RPC * kk + h) * C + t.c);
                 }
             }
         }
 #pragma unroll
-        for (int j = 0; j < U2; ++j) {
+        for (int j = 0; j < U; ++j) {
             const int kk = k + WAVES * j;
-            if (kk < k1 && t.act) {
+            if (kk < k1) {
                 u64 outb = 0;
-                h16x8 qh[2];
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
+                for (int h = 0; h < RPC; ++h) {
                     const h16x8 d = xv[j][h] - bv[j][h];
-                    const h16x8 dm = d - mn;                               // (r - min)
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        h16 v = hrint(hdiv_r(dm[i], scf[i], scr[i]));
-                        if (hisnan(v)) v = (h16)0;
-                        v = v < (h16)0 ? (h16)0 : v;
-                        v = v > (h16)15.0f ? (h16)15.0f : v;
-                        const unsigned qi = (unsigned)(float)v & 15u;
-                        qh[h][i] = (h16)(float)qi;
-                        outb |= (u64)qi << (8 * i + 4 * h);
-                    }
+                    for (int i = 0; i < 8; ++i) outb |= (u64)minmax_code<RPC>(d[i], mz[i], scf[i], scr[i]) << (8 * i + BITS * h);
                 }
                 *reinterpret_cast<u64*>(q + (size_t)kk * C + t.c) = outb;
-                if (upd) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
+                if (upd)
+                    unrolled<RPC>([&](int h) {
                         h16x8 o;
                         if (ef) {
-                            const h16x8 recv = qh[h] * sc + mn;            // q*scale + min (two roundings; contraction is off)
+                            const h16x8 recv = minmax_recv<RPC>(outb, h, sc, mz);
                             o = base ? (bv[j][h] + recv) : recv;
                         } else o = xv[j][h];
-                        st8nt(nb + (size_t)(2 * kk + h) * C + t.c, o);
-                    }
-                }
+                        st8nt(nb + (size_t)(RPC * kk + h) * C + t.c, o);
+                    });
             }
         }
     }
 }
 
-__global__ __launch_bounds__(NTHR) void k_int4_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
+template <int RPC>
+__global__ __launch_bounds__(NTHR) void k_minmax_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
+    constexpr int U = RPC == 1 ? UNROLL : 1;
     // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
     if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
     const cfx_decomp_item it = batch.it[blockIdx.z];
     const TileCoord t = tile_coord(N, C, R);
     const unsigned char* q = (const unsigned char*)it.packet;
-    const h16* S = (const h16*)(q + (size_t)(N / 2) * C);
-    const h16* M = S + C;
     const h16* base = (const h16*)it.base;
     h16* out = (h16*)it.recon;
-    const bool al16 = ((((uintptr_t)S) | ((uintptr_t)M)) & 15) == 0;
-    h16x8 sc = (h16x8)(h16)1.0f, mn = (h16x8)(h16)0;
-    if (t.act) { sc = ld8_tail(S + t.c, al16); mn = ld8_tail(M + t.c, al16); }
-    const int k0 = t.r0 >> 1, k1 = t.r1 >> 1;
-    constexpr int U2 = 1;   // one row PAIR per wave step
-    for (int k = k0 + t.w; k < k1; k += WAVES * U2) {
-        h16x8 bv[U2][2];
-        u64 qb[U2];
+    h16x8 sc, mz;
+    minmax_ld_scales_own<RPC>(q, N, C, t, sc, mz);
+    const int k1 = t.r1 / RPC;
+    for (int k = t.r0 / RPC + t.w; k < k1; k += WAVES * U) {
+        // the bounds guard of every access below: a lane whose 8 channels lie beyond C (t.act false) touches no memory.  One test per step,
+        // not one per load: the compiler then issues the loads of the next step under this step's stores (a guard around each load keeps
+        // them behind it; the 4-level kernels measured 1.3 % and 3.5 % slower that way)
+        if (!t.act) continue;
+        h16x8 bv[U][RPC];
+        u64 qb[U];
 #pragma unroll
-        for (int j = 0; j < U2; ++j) {
+        for (int j = 0; j < U; ++j) {
             const int kk = k + WAVES * j;
             qb[j] = 0;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < RPC; ++h) {
                 bv[j][h] = (h16x8)(h16)0;
-                if (kk < k1 && t.act && base) bv[j][h] = ld8nt(base + (size_t)(2 * kk + h) * C + t.c);
+                if (kk < k1 && base) bv[j][h] = ld8nt(base + (size_t)(RPC * kk + h) * C + t.c);
             }
-            if (kk < k1 && t.act) qb[j] = *reinterpret_cast<const u64*>(q + (size_t)kk * C + t.c);
+            if (kk < k1) qb[j] = *reinterpret_cast<const u64*>(q + (size_t)kk * C + t.c);
         }
 #pragma unroll
-        for (int j = 0; j < U2; ++j) {
+        for (int j = 0; j < U; ++j) {
             const int kk = k + WAVES * j;
-            if (kk < k1 && t.act) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    h16x8 qh;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) qh[i] = (h16)(float)((qb[j] >> (8 * i + 4 * h)) & 15u);
-                    const h16x8 recv = qh * sc + mn;
-                    st8nt(out + (size_t)(2 * kk + h) * C + t.c, base ? (bv[j][h] + recv) : recv);
-                }
-            }
-        }
-    }
-}
-
-// INT2_MINMAX quantise (+EF): k_int4_quant with four levels - one wave step handles the row QUAD (4k .. 4k+3), four rows per byte along N:
-// byte[k][c] = q[4k][c] | q[4k+1][c] << 2 | q[4k+2][c] << 4 | q[4k+3][c] << 6 (compress_quantize.py:406-424 gives the arithmetic; the
-// reference has no packing for it).  R (rows per tile) is a multiple of 4; quad index space = rows/4.
-__global__ __launch_bounds__(NTHR) void k_int2mm_quant(BatchC batch, int N, int C, int R, int flags) {
-    const cfx_comp_item it = batch.it[blockIdx.z];
-    const TileCoord t = tile_coord(N, C, R);
-    unsigned char* q = (unsigned char*)it.packet;
-    const h16* S = (const h16*)(q + (size_t)(N / 4) * C);
-    const h16* M = S + C;
-    const h16* x = (const h16*)it.x;
-    const h16* base = (const h16*)it.base;
-    h16* nb = (h16*)it.new_base;
-    const bool upd = (flags & CFX_FLAG_UPDATE_CACHE) && nb;
-    const bool ef = !(flags & CFX_FLAG_NO_EF);
-    const bool al16 = ((((uintptr_t)S) | ((uintptr_t)M)) & 15) == 0;
-    h16x8 sc = (h16x8)(h16)1.0f, mn = (h16x8)(h16)0;
-    if (t.act) { sc = ld8_tail(S + t.c, al16); mn = ld8_tail(M + t.c, al16); }
-    float scf[8], scr[8];                                    // the channel's scale and its reciprocal: hdiv_r
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { scf[i] = (float)sc[i]; scr[i] = __builtin_amdgcn_rcpf(scf[i]); }
-    const int k0 = t.r0 >> 2, k1 = t.r1 >> 2;
-    for (int k = k0 + t.w; k < k1; k += WAVES) {             // one row QUAD per wave step
-        if (!t.act) continue;
-        h16x8 xv[4], bv[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            xv[h] = ld8nt(x + (size_t)(4 * k + h) * C + t.c);
-            bv[h] = base ? ld8nt(base + (size_t)(4 * k + h) * C + t.c) : (h16x8)(h16)0;
-        }
-        u64 outb = 0;
-        h16x8 qh[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const h16x8 d = xv[h] - bv[h];
-            const h16x8 dm = d - mn;                         // (r - min)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                h16 v = hrint(hdiv_r(dm[i], scf[i], scr[i]));
-                if (hisnan(v)) v = (h16)0;
-                v = v < (h16)0 ? (h16)0 : v;
-                v = v > (h16)3.0f ? (h16)3.0f : v;
-                const unsigned qi = (unsigned)(float)v & 3u;
-                qh[h][i] = (h16)(float)qi;
-                outb |= (u64)qi << (8 * i + 2 * h);
-            }
-        }
-        *reinterpret_cast<u64*>(q + (size_t)k * C + t.c) = outb;
-        if (upd) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                h16x8 o;
-                if (ef) {
-                    const h16x8 recv = qh[h] * sc + mn;      // q*scale + min (two roundings; contraction is off)
-                    o = base ? (bv[h] + recv) : recv;
-                } else o = xv[h];
-                st8nt(nb + (size_t)(4 * k + h) * C + t.c, o);
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(NTHR) void k_int2mm_dequant(BatchD batch, int N, int C, int R, unsigned* pre, unsigned pre_val) {
-    // lane: publish `pre` first - the launch in front of this one in the stream (the previous peer's reconstruction) has finished
-    if (pre && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) st_wt(pre, pre_val);
-    const cfx_decomp_item it = batch.it[blockIdx.z];
-    const TileCoord t = tile_coord(N, C, R);
-    const unsigned char* q = (const unsigned char*)it.packet;
-    const h16* S = (const h16*)(q + (size_t)(N / 4) * C);
-    const h16* M = S + C;
-    const h16* base = (const h16*)it.base;
-    h16* out = (h16*)it.recon;
-    const bool al16 = ((((uintptr_t)S) | ((uintptr_t)M)) & 15) == 0;
-    h16x8 sc = (h16x8)(h16)1.0f, mn = (h16x8)(h16)0;
-    if (t.act) { sc = ld8_tail(S + t.c, al16); mn = ld8_tail(M + t.c, al16); }
-    const int k0 = t.r0 >> 2, k1 = t.r1 >> 2;
-    for (int k = k0 + t.w; k < k1; k += WAVES) {             // one row QUAD per wave step
-        if (!t.act) continue;
-        h16x8 bv[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) bv[h] = base ? ld8nt(base + (size_t)(4 * k + h) * C + t.c) : (h16x8)(h16)0;
-        const u64 qb = *reinterpret_cast<const u64*>(q + (size_t)k * C + t.c);
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            h16x8 qh;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) qh[i] = (h16)(float)((qb >> (8 * i + 2 * h)) & 3u);
-            const h16x8 recv = qh * sc + mn;
-            st8nt(out + (size_t)(4 * k + h) * C + t.c, base ? (bv[h] + recv) : recv);
+            if (kk < k1)
+                unrolled<RPC>([=](int h) {            // (by value: by reference the compiler keeps 6 registers more)
+                    const h16x8 recv = minmax_recv<RPC>(qb[j], h, sc, mz);
+                    st8nt(out + (size_t)(RPC * kk + h) * C + t.c, base ? (bv[j][h] + recv) : recv);
+                });
         }
     }
 }
@@ -1046,31 +855,33 @@ __global__ __launch_bounds__(NTHR) void k_int2mm_dequant(BatchD batch, int N, in
 // ---------------------------------------------------------------------------------------------------
 // host side: this family's launches (validated and dispatched by cfx_api.hip)
 // ---------------------------------------------------------------------------------------------------
+// the family's kernels instantiated for a member (rpc: 1, 2 or 4)
+typedef void (*MinMaxLayerFn)(BatchC, BatchD, MinMaxLayerArgs);
+typedef void (*MinMaxQuantFn)(BatchC, int, int, int, int);
+typedef void (*MinMaxDequantFn)(BatchD, int, int, int, unsigned*, unsigned);
+static MinMaxLayerFn minmax_layer_kernel(int rpc, int RL) {     // RL: the S tile's height, 32 or 64 rows
+    if (RL == 32) return rpc == 2 ? k_minmax_layer<2, 4> : rpc == 4 ? k_minmax_layer<4, 4> : k_minmax_layer<1, 4>;
+    return rpc == 2 ? k_minmax_layer<2, 8> : rpc == 4 ? k_minmax_layer<4, 8> : k_minmax_layer<1, 8>;
+}
+static MinMaxQuantFn minmax_quant_kernel(int rpc) { return rpc == 2 ? k_minmax_quant<2> : rpc == 4 ? k_minmax_quant<4> : k_minmax_quant<1>; }
+static MinMaxDequantFn minmax_dequant_kernel(int rpc) { return rpc == 2 ? k_minmax_dequant<2> : rpc == 4 ? k_minmax_dequant<4> : k_minmax_dequant<1>; }
+
 int cfx_i_minmax_compress(CompressCall& cc) {
     cfx_ctx* ctx = cc.ctx;
-    const int codec = cc.codec, N = cc.N, C = cc.C, param = cc.param, flags = cc.flags, batch = cc.batch, n_ride = cc.n_ride, CB = cc.CB;
+    const int codec = cc.codec, N = cc.N, C = cc.C, flags = cc.flags, batch = cc.batch, CB = cc.CB;
     int n_gated = cc.n_gated;
-    const cfx_comp_item* items = cc.items;
     const cfx_decomp_item* gated = cc.gated;
     void* stream = cc.stream;
     hipStream_t s = (hipStream_t)stream;
     CfxXGate* xg = cc.xg;
     BatchC b = cc.b;
-    BatchD rd = cc.rd, gd = cc.gd;
-    u64* ws = cc.ws;
-    const size_t wstride = cc.wstride;
-    const bool upd = cc.upd, capturing = cc.capturing;
-    (void)param; (void)n_ride; (void)items; (void)gated; (void)rd; (void)ws; (void)wstride; (void)upd; (void)capturing; (void)xg; (void)gd;
+    BatchD gd = cc.gd;
     const bool fused = cc.fused;
-    unsigned* tick = cc.tick;
     const unsigned slot = cc.slot;
     const int stream_cus = cc.stream_cus, R = cc.R, P = cc.P;
-    (void)tick; (void)slot;
-    const dim3 grid(CB, P, batch);
     int Rq = auto_rows(ctx, N, C, batch, true);             // apply passes: same tile map as the (unfused) statistics pass
     if (codec == CFX_CODEC_INT2_MINMAX) Rq = (Rq + 3) & ~3; // (a row quad never straddles a tile: tile starts are multiples of 4, as they are even for int4)
     const dim3 gridq(CB, (N + Rq - 1) / Rq, batch);
-    (void)grid;
     // ---- the min/max codecs' layer in ONE launch (k_minmax_layer): statistics tile in registers, in-launch scales, codes from registers,
     // gated reconstruction.  Needs every statistics workgroup CO-RESIDENT on the stream's CUs (each waits for its column block's scales
     // holding its tile); otherwise - tall tensors - the multi-launch forms below run (identical results). ----
@@ -1084,7 +895,7 @@ int cfx_i_minmax_compress(CompressCall& cc) {
     const long n_st = (long)CB * PL * batch;
     long n_g = (long)CB * g_rb * n_gated;
     bool layer = fused && ctx->gated_on && !ctx->dev_probe && C % 16 == 0 && stream_cus >= 128 && ctx->stats_rows == 0 && PL <= MML_MAX_P_TALL &&
-                 n_st <= MML_MAX_TILES && !capturing;
+                 n_st <= MML_MAX_TILES && !cc.capturing;
     if (layer && !n_gated && !xg) {
         // a plain compress call may be under stream capture (the ungated launches are capturable: include/cfx.h); the layer launch is not -
         // its tags and flags are launch arguments that advance with every launch, a replayed node would meet its own old tags
@@ -1099,7 +910,7 @@ int cfx_i_minmax_compress(CompressCall& cc) {
         for (int g_ = 0; g_ < n_gated && layer; ++g_) {
             int m = -1;
             for (int i = 0; i < batch; ++i)
-                if (gated[g_].packet == items[i].packet) m = i;
+                if (gated[g_].packet == cc.items[i].packet) m = i;
             if (m < 0) layer = false;
             src[g_] = (signed char)m;
         }
@@ -1107,11 +918,9 @@ int cfx_i_minmax_compress(CompressCall& cc) {
     if (layer) {
         static int per_cu_of[3] = {0, 0, 0};
         int& per_cu = per_cu_of[rpc >> 1];
-        if (!per_cu) {
-            const hipError_t oe = rpc == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer<true, 8>, FUSED_NT, 0)
-                                  : rpc == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer4<8>, FUSED_NT, 0)
-                                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_minmax_layer<false, 8>, FUSED_NT, 0);
-            if (oe != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+        if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, minmax_layer_kernel(rpc, 64), FUSED_NT, 0) != hipSuccess || per_cu < 1)) {
+            (void)hipGetLastError();
+            per_cu = 1;
         }
         const long slots = (long)per_cu * stream_cus;
         // every S tile co-resident; or - tall form - a column block's P tiles at a time, which in-order dispatch (workgroup i on XCD
@@ -1144,29 +953,8 @@ int cfx_i_minmax_compress(CompressCall& cc) {
         // later launch expects, so it starts zeroed and only ever takes this context's sequence numbers (which are not reused)
         a.part_stride = (size_t)(PL + 1) * C;
         const size_t need = a.part_stride * batch * sizeof(u64);
-        if (!ctx->mml_arena_owned[ring] || ctx->mml_arena_owner[ring] != stream) {
-            // the ring - and with it the arena - changed hands (more than CFX_RING_STREAMS streams issue compress launches): whatever its
-            // previous owner still has in flight reads this arena.  Rare by construction; wait for it
-            if (ctx->mml_arena_owned[ring]) (void)hipDeviceSynchronize();
-            ctx->mml_arena_owner[ring] = stream;
-            ctx->mml_arena_owned[ring] = true;
-        }
-        if (ctx->mml_arena_bytes[ring] < need) {
-            if (ctx->mml_arena[ring]) (void)hipFree(ctx->mml_arena[ring]);      // (synchronises the device: no launch still reads it)
-            ctx->mml_arena[ring] = nullptr;
-            ctx->mml_arena_bytes[ring] = 0;
-            const size_t cap = (std::max(need, (size_t)4 << 20) + 4095) & ~(size_t)4095;
-            void* m = nullptr;
-            // (zeroed IN the launch stream: a plain hipMemset runs on the NULL stream, which a non-blocking stream does not wait for)
-            if (hipMalloc(&m, cap) != hipSuccess || hipMemsetAsync(m, 0, cap, s) != hipSuccess) {
-                (void)hipGetLastError();
-                if (m) (void)hipFree(m);
-                return fail(ctx, CFX_ERR_LAUNCH, "min/max layer launch: cannot allocate the partials' arena");
-            }
-            ctx->mml_arena[ring] = (u64*)m;
-            ctx->mml_arena_bytes[ring] = cap;
-        }
-        a.part = ctx->mml_arena[ring];
+        a.part = ring_arena_reserve(ctx, ring, stream, &ctx->mml_arena[ring], &ctx->mml_arena_bytes[ring], need, (size_t)4 << 20);
+        if (!a.part) return fail(ctx, CFX_ERR_LAUNCH, "min/max layer launch: cannot allocate the partials' arena");
         a.probe = cfx_i_probe(ctx);
         a.codedone = ctx->colgate + (size_t)ring * MML_MAX_TILES;
         a.tall = tall ? 1 : 0;
@@ -1197,28 +985,18 @@ int cfx_i_minmax_compress(CompressCall& cc) {
             xg->f_gate = a.xgate; xg->f_expect = a.xexpect;
         }
         const dim3 g((unsigned)(n_st + n_g));
-        if (RL == 32) {
-            if (rpc == 2) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<true, 4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
-            else if (rpc == 4) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer4<4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
-            else LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<false, 4>), g, dim3(FUSED_NT), 0, s, b, gd, a);
-        } else {
-            if (rpc == 2) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<true, 8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
-            else if (rpc == 4) LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer4<8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
-            else LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, (k_minmax_layer<false, 8>), g, dim3(FUSED_NT), 0, s, b, gd, a);
-        }
+        LAUNCH(ctx, KID_ABSMEAN_COMPRESS_GATED, s, minmax_layer_kernel(rpc, RL), g, dim3(FUSED_NT), 0, s, b, gd, a);
         return check_launch(ctx, "min/max layer launch");
     }
     if (fused) {
-        LAUNCH(ctx, KID_MINMAX_COMPRESS, s, k_minmax_compress, dim3(CB * P * batch), dim3(NTHR), 0, s, b, N, C, R, CB, P, codec, ws, wstride, tick);
+        LAUNCH(ctx, KID_MINMAX_COMPRESS, s, k_minmax_compress, dim3(CB * P * batch), dim3(NTHR), 0, s, b, N, C, R, CB, P, codec, cc.ws, cc.wstride, cc.tick);
     } else {
-        LAUNCH(ctx, KID_MINMAX_STATS, s, k_minmax_stats, grid, dim3(NTHR), 0, s, b, N, C, R, ws, wstride);
-        LAUNCH(ctx, KID_MINMAX_FINALIZE, s, k_minmax_finalize, dim3((C + 255) / 256, batch), dim3(1024), 0, s, b, N, C, P, codec, (const u64*)ws, wstride);
+        LAUNCH(ctx, KID_MINMAX_STATS, s, k_minmax_stats, dim3(CB, P, batch), dim3(NTHR), 0, s, b, N, C, R, cc.ws, cc.wstride);
+        LAUNCH(ctx, KID_MINMAX_FINALIZE, s, k_minmax_finalize, dim3((C + 255) / 256, batch), dim3(1024), 0, s, b, N, C, P, codec, (const u64*)cc.ws, cc.wstride);
     }
-    if (codec == CFX_CODEC_INT4) LAUNCH(ctx, KID_INT4_QUANT, s, k_int4_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
-    else if (codec == CFX_CODEC_INT2_MINMAX) LAUNCH(ctx, KID_INT4_QUANT, s, k_int2mm_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
-    else LAUNCH(ctx, KID_INT8_QUANT, s, k_int8_quant, gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
+    LAUNCH(ctx, rpc == 1 ? KID_INT8_QUANT : KID_INT4_QUANT, s, minmax_quant_kernel(rpc), gridq, dim3(NTHR), 0, s, b, N, C, Rq, flags);
     if (n_gated) {
-        const int rcg = decompress_impl(ctx, codec, N, C, param, n_gated, gated, stream, nullptr, 0u);
+        const int rcg = decompress_impl(ctx, codec, N, C, cc.param, n_gated, gated, stream, nullptr, 0u);
         if (rcg != CFX_OK) return rcg;
     }
     return check_launch(ctx, "compress launch");
@@ -1230,8 +1008,7 @@ int cfx_i_minmax_decompress(const DecompressCall& dc) {
     hipStream_t s = (hipStream_t)dc.stream;
     const int R = codec == CFX_CODEC_INT2_MINMAX ? (dc.R + 3) & ~3 : dc.R;   // (row quads: see cfx_i_minmax_compress)
     const dim3 grid((C + TILE_C - 1) / TILE_C, (N + R - 1) / R, dc.batch);
-    if (codec == CFX_CODEC_INT4) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int4_dequant, grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
-    else if (codec == CFX_CODEC_INT2_MINMAX) LAUNCH(ctx, KID_INT4_DEQUANT, s, k_int2mm_dequant, grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
-    else LAUNCH(ctx, KID_INT8_DEQUANT, s, k_int8_dequant, grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
+    const int rpc = mml_rpc(codec);
+    LAUNCH(ctx, rpc == 1 ? KID_INT8_DEQUANT : KID_INT4_DEQUANT, s, minmax_dequant_kernel(rpc), grid, dim3(NTHR), 0, s, dc.b, N, C, R, dc.pre, dc.pre_val);
     return check_launch(ctx, "decompress launch");
 }

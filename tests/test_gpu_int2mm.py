@@ -392,7 +392,7 @@ def _replay(seqs, N, C, ef=True):
 @pytest.mark.parametrize("api", ["ring", "gather"])
 def test_plugin_call_one_layer_launch_per_layer(loop8, api, ef):
     """INT2_MINMAX through compact_fwd / compact_all_gather_kv with the lane off: ONE native op per layer, and that op is ONE codec launch
-    (kernel id 31: k_minmax_layer4 with the peer-to-peer exchange inside) - no quantise (11), dequantise (12) or statistics (7, 8, 29)
+    (kernel id 31: k_minmax_layer<4, RW> with the peer-to-peer exchange inside) - no quantise (11), dequantise (12) or statistics (7, 8, 29)
     launch; every logical rank's state against the contract's replay bit for bit"""
     ring, cm, xlayer = loop8
     from compactfusion_amd import _lib, codecs as K

@@ -13,7 +13,7 @@ import torch
 
 from compactfusion_amd import _lib, codecs as K
 
-ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (None, None)}
+ALG = {1: (6.125, 4.125), 2: (6.25, 4.25), 3: (6.5, 4.5), 4: (7.0, 5.0), 5: (None, None), 6: (6.25, 4.25)}
 
 
 def read_prof(lib, ctx, cap=100000):
@@ -36,10 +36,13 @@ def main():
     ap.add_argument("--dbatch", type=int, default=14)
     ap.add_argument("--sets", type=int, default=24, help="distinct tensor sets cycled through (cold HBM)")
     ap.add_argument("--iters", type=int, default=96)
+    ap.add_argument("--launches", action="store_true", help="cfx_set_gated_launch(ctx, 0): the stand-alone launches where a layer launch would run")
     args = ap.parse_args()
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     ctx = K.context(0)
+    if args.launches:
+        assert lib.cfx_set_gated_launch(ctx, 0) == 0
     N, C = args.N, args.C
     s = torch.cuda.current_stream().cuda_stream
     # copy probe
