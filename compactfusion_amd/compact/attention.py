@@ -142,8 +142,9 @@ def attention_blocks(q, ks, vs, softmax_scale: Optional[float] = None) -> Tuple[
     """The attention of q (B, Sq, H, D) over ALL the K,V blocks ks[i], vs[i] (B, Sk, H, D) - non-causal, no dropout - as if they were
     one sequence: out (B, Sq, H, D) in q.dtype, lse fp32 as the (B, H, Sq) view of a (B, Sq, H) tensor.  Nothing is concatenated and no
     per-block out / lse exists (include/cfx.h, cfx_attn_fwd_blocks, states the arithmetic rounding by rounding).
-    On the GPU - q and every block fp16 or bf16 alike, contiguous, 16-byte aligned, on one device, D 64 or 128, the blocks of one shape
-    that agrees with q in B, H and D - this is ONE native launch.  The launch takes at most 16 blocks: more on the native path are
+    On the GPU - q and every block fp16 or bf16 alike, contiguous, 16-byte aligned, on one device, D 64 or 128, the blocks agreeing with q
+    in B, H and D - this is ONE native launch: cfx_attn_fwd_blocks for blocks of one shape, cfx_attn_fwd_blocks_var for blocks that
+    differ in their key count (ks[i] (B, Sk_i, H, D)).  The launch takes at most 16 blocks: more on the native path are
     REFUSED (ValueError), as `merge_blocks` refuses them.  Anything else (CPU tensors: the host-logic tests; other types, head dims or
     layouts) runs the direct definition in eager fp32 torch."""
     n = len(ks)
@@ -157,6 +158,12 @@ def attention_blocks(q, ks, vs, softmax_scale: Optional[float] = None) -> Tuple[
             raise ValueError(f"attention_blocks: {n} blocks - the one-launch attention takes at most {_lib.ATTN_MAX_BLOCKS} "
                              "(configure(attention='sdpa') attends to any number)")
         return _attn_fwd_native(q, ks, vs, softmax_scale)
+    if attn_native_var_ok(q, ks, vs):                                                         # blocks that differ in their key count only
+        from .. import _lib
+        if n > _lib.ATTN_MAX_BLOCKS:
+            raise ValueError(f"attention_blocks: {n} blocks - the one-launch attention takes at most {_lib.ATTN_MAX_BLOCKS} "
+                             "(configure(attention='sdpa') attends to any number)")
+        return _attn_fwd_native_var(q, ks, vs, softmax_scale)
     qt = q.float().transpose(1, 2)                                                            # (B, H, Sq, D)
     s = torch.cat([torch.matmul(qt, k.float().permute(0, 2, 3, 1)) for k in ks], dim=-1) * softmax_scale
     m = s.max(dim=-1, keepdim=True).values
@@ -180,7 +187,14 @@ def attn_native_ok(q, ks, vs) -> bool:
                for t in list(ks) + list(vs))
 
 
+def attn_native_var_ok(q, ks, vs) -> bool:
+    """whether `attention_blocks` takes (q, ks, vs) to the native launch for blocks of unequal length (cfx_attn_fwd_blocks_var; the
+    number of blocks aside): `attn_native_ok`'s conditions block by block - K and V of a block of one shape - with the key count free"""
+    return len(ks) == len(vs) and all(k.dim() == 4 and k.shape == v.shape and attn_native_ok(q, (k,), (v,)) for k, v in zip(ks, vs))
+
+
 _attn_fwd_fn = None
+_attn_var_fn = None
 
 
 def _attn_fwd_native(q, ks, vs, softmax_scale, tabs=None):
@@ -207,8 +221,32 @@ def _attn_fwd_native(q, ks, vs, softmax_scale, tabs=None):
     return out, lse.transpose(1, 2)
 
 
+def _attn_fwd_native_var(q, ks, vs, softmax_scale, tabs=None):
+    """the launch for blocks of unequal length, on arguments `attn_native_var_ok` passed; `tabs`: the caller's three ctypes tables - K
+    pointers, V pointers, key counts (compact/ring.py keeps a layer's) -, built here otherwise"""
+    global _attn_var_fn
+    import ctypes
+    from .. import _lib, codecs
+    n = len(ks)
+    B, Sq, H, D = q.shape
+    dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    if _attn_var_fn is None:
+        _attn_var_fn = _lib.load().cfx_attn_fwd_blocks_var
+    if tabs is None:
+        P = ctypes.c_void_p * n
+        tabs = P(*[t.data_ptr() for t in ks]), P(*[t.data_ptr() for t in vs]), (ctypes.c_int * n)(*[t.shape[1] for t in ks])
+    out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, Sq, H), dtype=torch.float32, device=q.device)
+    ctx = codecs.context(dev)
+    rc = _attn_var_fn(ctx, n, q.data_ptr(), tabs[0], tabs[1], tabs[2], B, Sq, H, D, softmax_scale,
+                      _lib.ELEM_BF16 if q.dtype == torch.bfloat16 else 0, out.data_ptr(), lse.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        codecs._check(ctx, rc, "cfx_attn_fwd_blocks_var")
+    return out, lse.transpose(1, 2)
+
+
 def attn_fwd_launches(device=None) -> int:
-    """cfx_attn_fwd_blocks launches enqueued so far on the device's context (the launch carries no kernel id: the context counts)"""
+    """cfx_attn_fwd_blocks / cfx_attn_fwd_blocks_var launches enqueued so far on the device's context (the launch carries no kernel id: the context counts)"""
     import ctypes
     from .. import _lib, codecs
     dev = torch.cuda.current_device() if device is None else (device.index if isinstance(device, torch.device) else device)

@@ -26,7 +26,7 @@ from .. import config as _settings
 from ..collector import collector as _collector_mod
 from ..prof import Profiler
 from . import main as cm
-from .attention import _attn_fwd_native, attn_native_ok, block_attention, flag_wait, merge_blocks, update_out_and_lse
+from .attention import _attn_fwd_native, _attn_fwd_native_var, attn_native_ok, block_attention, flag_wait, merge_blocks, update_out_and_lse
 from .main import compact_cache, compact_compress, compact_config, compact_decompress
 from .utils import COMPACT_COMPRESS_TYPE
 
@@ -181,6 +181,12 @@ def _with_joint(k, v, jk, jv, mode, step, world):
     return k, v
 
 
+def _joint_agrees(q, jk, jv) -> bool:
+    """a joint K,V pair the steady layer can attend over beside its blocks: q's B, H, D, element type and device, any length"""
+    return (jk.dim() == 4 and jk.shape == jv.shape and jk.shape[1] > 0 and (jk.shape[0], jk.shape[2], jk.shape[3]) == (q.shape[0], q.shape[2], q.shape[3])
+            and jk.dtype == q.dtype and jv.dtype == q.dtype and jk.device == q.device and jv.device == q.device)
+
+
 def _schedule(q: torch.Tensor) -> str:
     s = _settings.get("ring_schedule")
     if s == "auto":
@@ -199,11 +205,21 @@ def _compact_ring_fwd(q, k, v, dropout_p=0, softmax_scale=None, causal=True, win
     # native calls around the local attention block, no per-call bookkeeping (the reference rebuilds keys, shapes and
     # communicator state on every call, ring.py:172-190)
     st = _steady.get((mod_idx, id(group) if group is not None else None))
-    if st is not None and joint_tensor_key is None and joint_tensor_value is None:
+    joint = None
+    if st is not None and (joint_tensor_key is not None or joint_tensor_value is not None):
+        # joint tensors (the text keys every rank holds): the general path below unless configure(joint="steady") and the pair is
+        # well-formed (`_joint_mode`: the errors of the general path) and agrees with q in everything but its length
+        if _settings.get("joint") != "steady":
+            st = None
+        else:
+            joint = (joint_tensor_key, joint_tensor_value, _joint_mode(joint_tensor_key, joint_tensor_value, joint_strategy))
+            if not _joint_agrees(q, joint_tensor_key, joint_tensor_value):
+                st = None
+    if st is not None:
         cfg = compact_config()
         ctype = cfg.compress_func(mod_idx, current_iter)
         if st.matches(q, k, v, ctype, cfg, causal, dropout_p):
-            return st.run(q, k, v, softmax_scale)
+            return st.run(q, k, v, softmax_scale) if joint is None else st.run(q, k, v, softmax_scale, joint)
     jmode = _joint_mode(joint_tensor_key, joint_tensor_value, joint_strategy)
     comm = RingComm(group)
     rank, world = comm.rank, comm.world_size
@@ -263,6 +279,7 @@ class _SteadyLayer:
     _fast = None                 # `_fast_ok`'s answer, once asked
     _fwait = None                # cfx_flag_wait, bound at the first attn_merge="once" call of a lane form
     _native = None               # `_native_ok`'s answer for the peers' states, once asked
+    _jtabs = None                # joint strategy -> the tables of the one launch with the joint block in (`_joint_tabs`), once built
 
     def __init__(self, ex, q, k, v, ctype, cfg, rank, world):
         cache = compact_cache()
@@ -313,7 +330,9 @@ class _SteadyLayer:
             self._fast = False
         return self._fast
 
-    def run(self, q, k, v, softmax_scale):
+    def run(self, q, k, v, softmax_scale, joint=None):
+        """joint: (joint K, joint V, "front" | "rear") of a call with joint tensors (configure(joint="steady")) - local to the rank, never
+        compressed or sent: the exchange below does not know of it, only the blocks do"""
         ex, xop = self.ex, self.ex.xop
         sh = torch.cuda.current_stream(q.device).cuda_stream
         if xop is None:
@@ -333,7 +352,7 @@ class _SteadyLayer:
                     ex.run_lane(k, v, None)
                 elif s == 1 and lean:
                     ex.run_lane_tail()
-            return self._blocks(q, k, v, softmax_scale, sh, issue, ex.flag_ptr, epoch)
+            return self._blocks(q, k, v, softmax_scale, sh, issue, ex.flag_ptr, epoch, joint)
         # ONE native call: the layer's whole exchange on this stream, then the blocks over own K,V and the peers' states
         lane = False
         if xop.lowrank and xop.lane_capable():
@@ -344,12 +363,27 @@ class _SteadyLayer:
         epoch = xop.run(k, v, sh, lane)
         cm._current_cache_key = self.last_key
         if epoch is None:
-            return self._blocks(q, k, v, softmax_scale, sh)
+            return self._blocks(q, k, v, softmax_scale, sh, None, None, 0, joint)
         # peers 1 and 2 while the local block runs, peer s + 2 behind peer s's block
         return self._blocks(q, k, v, softmax_scale, sh, lambda s, lean: xop.lane_chain(1, 2) if s == 0 else xop.lane_chain(s + 2, 1),
-                            xop.lane_flag, epoch)
+                            xop.lane_flag, epoch, joint)
 
-    def _blocks(self, q, k, v, softmax_scale, sh, issue=None, flag=None, epoch=0):
+    def _block_list(self, k, v, joint, lean):
+        """(ring step, K, V) of the block loops: own K,V, then the peers' states - as the fused op's (B, H, S, D) views when lean.  joint:
+        block 0 attends [joint ; own] (front) or block W-1 [peer ; joint] (rear), what `_with_joint` gives the general path.
+        A GENERATOR: a block is formed when the loop reaches it - on the lane forms peer W-1's state is complete only behind the wait
+        block W-2 carries, and the concatenation that reads it must be enqueued behind that wait like the block's attention itself."""
+        blocks = [(0, k.transpose(1, 2), v.transpose(1, 2))] + self._peer_t if lean else [(0, k, v)] + self._peers
+        at = None if joint is None else (0 if joint[2] == "front" else self.world - 1)
+        for s, kk, vv in blocks:
+            if s == at:
+                kk, vv = (k, v) if s == 0 else self._peers[-1][1:]
+                kk, vv = _with_joint(kk, vv, joint[0], joint[1], joint[2], s, self.world)
+                if lean:
+                    kk, vv = kk.transpose(1, 2), vv.transpose(1, 2)
+            yield s, kk, vv
+
+    def _blocks(self, q, k, v, softmax_scale, sh, issue=None, flag=None, epoch=0, joint=None):
         """The layer's attention blocks in ring order - own K,V, then peer s = 1 .. W-1 - merged into one running out / lse.  The lane
         forms pass `issue` and `flag`: after block s, issue(s, lean) issues the chain launches that belong behind it, and the merge of
         block s < W-1 also waits, inside its launch, until flag(s + 1) - peer s+1 reconstructed - has reached `epoch`.  lean
@@ -362,12 +396,14 @@ class _SteadyLayer:
         stand-alone cfx_flag_wait behind block s (s < W-1), issue(s, lean) is called where it always was, and what is returned has the
         chain's types, shapes and views.
         configure(attention="native"), where the launch takes the layer (`_native_ok`): no SDPA call and no merge at all - ONE
-        cfx_attn_fwd_blocks launch over own K,V and the peers' states where they lie (`_blocks_native`); attn_merge is ignored."""
+        cfx_attn_fwd_blocks launch over own K,V and the peers' states where they lie (`_blocks_native`); attn_merge is ignored.
+        joint (`run`): the sdpa forms attend it with block 0 or W-1 (`_block_list`), everything else - waits and `issue` calls included -
+        unchanged; the native form puts it into the one launch as a block of its own length (cfx_attn_fwd_blocks_var)."""
         last = self.world - 1
-        if _settings.get("attention") == "native" and self._native_ok(q, k, v):
-            return self._blocks_native(q, k, v, softmax_scale, issue, flag, epoch)
+        if _settings.get("attention") == "native" and (self._native_ok(q, k, v) if joint is None else self._native_joint_ok(q, k, v, joint)):
+            return self._blocks_native(q, k, v, softmax_scale, issue, flag, epoch, joint)
         if _settings.get("attn_merge") == "once":
-            return self._blocks_once(q, k, v, softmax_scale, sh, issue, flag, epoch)
+            return self._blocks_once(q, k, v, softmax_scale, sh, issue, flag, epoch, joint)
         if self._fast_ok(q):
             sdpa, merge, ctx, mflags = self._sdpa, self._merge, self._ctx, self._mflags
             B, S, H, D = q.shape
@@ -377,7 +413,7 @@ class _SteadyLayer:
             lse = torch.empty((B, S, H, 1), dtype=torch.float32, device=q.device)
             ap, op, lp = acc.data_ptr() if last else None, out.data_ptr(), lse.data_ptr()
             keep = []                                       # the SDPA results, held until their merges are enqueued
-            for s, kt, vt in [(0, k.transpose(1, 2), v.transpose(1, 2))] + self._peer_t:
+            for s, kt, vt in self._block_list(k, v, joint, True):
                 res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
                 keep.append(res)
                 wait = None
@@ -391,7 +427,7 @@ class _SteadyLayer:
                     raise RuntimeError("cfx_attn_merge_ex failed: " + (_lib.load().cfx_last_error_string(ctx) or b"").decode())
             return out, lse.squeeze(dim=-1).transpose(1, 2), None
         out = lse = None
-        for s, kk, vv in [(0, k, v)] + self._peers:
+        for s, kk, vv in self._block_list(k, v, joint, False):
             bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
             wait = None
             if issue is not None:
@@ -415,22 +451,53 @@ class _SteadyLayer:
                 self._nks, self._nvs = [None] + pk, [None] + pv
         return self._native and attn_native_ok(q, (k,), (v,))
 
-    def _blocks_native(self, q, k, v, softmax_scale, issue, flag, epoch):
+    def _native_joint_ok(self, q, k, v, joint) -> bool:
+        """`_native_ok` for a call with joint tensors: one block more - W + 1 in all - and the joint pair asked like the call's own K,V"""
+        from .. import _lib
+        return self.world + 1 <= _lib.ATTN_MAX_BLOCKS and self._native_ok(q, k, v) and attn_native_ok(q, (joint[0],), (joint[1],))
+
+    def _joint_tabs(self, mode):
+        """The tables of the one launch with the joint block in - [joint, own, peers...] (front) or [own, peers..., joint] (rear): K
+        pointers, V pointers, key counts, and the tensor lists beside them.  The peers' entries are set once per layer and strategy (with
+        `_native_ok`'s tables: the arena's addresses stand while the layer is steady), the joint and own entries by every call.
+        Returns (tables, K list, V list, index of the joint block, index of the own block)."""
+        if self._jtabs is None:
+            self._jtabs = {}
+        ent = self._jtabs.get(mode)
+        if ent is None:
+            import ctypes
+            n, first = self.world + 1, 1 if mode == "front" else 0          # first: where the own block sits, the peers behind it
+            pk, pv = self._nks[1:], self._nvs[1:]
+            tk, tv, tn = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), (ctypes.c_int * n)()
+            lk, lv = [None] * n, [None] * n
+            for i, (a, b) in enumerate(zip(pk, pv), start=first + 1):
+                tk[i], tv[i], tn[i], lk[i], lv[i] = a.data_ptr(), b.data_ptr(), a.shape[1], a, b
+            ent = self._jtabs[mode] = ((tk, tv, tn), lk, lv, 0 if mode == "front" else n - 1, first)
+        return ent
+
+    def _blocks_native(self, q, k, v, softmax_scale, issue, flag, epoch, joint=None):
         """`_blocks` with configure(attention="native").  The launch reads every peer's state, so on the lane forms the layer's whole
         chain is issued first - issue(s, lean) for s = 0 .. W-1, in the order the blocks would have called it - then a stand-alone
-        cfx_flag_wait on each of flag(1 .. W-1), then the launch: inside a layer the lane overlaps nothing with it."""
+        cfx_flag_wait on each of flag(1 .. W-1), then the launch: inside a layer the lane overlaps nothing with it.
+        joint: the same, the launch being cfx_attn_fwd_blocks_var over `_joint_tabs`' W + 1 blocks."""
         if issue is not None:
             for s in range(self.world):
                 issue(s, True)
             for s in range(1, self.world):
                 flag_wait((flag(s), epoch), q.device)
+        if joint is not None:
+            tabs, lk, lv, ji, oi = self._joint_tabs(joint[2])
+            for i, kk, vv in ((ji, joint[0], joint[1]), (oi, k, v)):
+                tabs[0][i], tabs[1][i], tabs[2][i], lk[i], lv[i] = kk.data_ptr(), vv.data_ptr(), kk.shape[1], kk, vv
+            out, lse = _attn_fwd_native_var(q, lk, lv, softmax_scale, tabs)
+            return out, lse, None
         tk, tv = self._ntabs
         tk[0], tv[0] = k.data_ptr(), v.data_ptr()
         self._nks[0], self._nvs[0] = k, v
         out, lse = _attn_fwd_native(q, self._nks, self._nvs, softmax_scale, self._ntabs)
         return out, lse, None
 
-    def _blocks_once(self, q, k, v, softmax_scale, sh, issue, flag, epoch):
+    def _blocks_once(self, q, k, v, softmax_scale, sh, issue, flag, epoch, joint=None):
         """`_blocks` with configure(attn_merge="once"): the lean path and the general one"""
         last = self.world - 1
         outs, lses = [], []
@@ -440,7 +507,7 @@ class _SteadyLayer:
                 from .. import _lib
                 self._fwait = _lib.load().cfx_flag_wait
             qt = q.transpose(1, 2)
-            for s, kt, vt in [(0, k.transpose(1, 2), v.transpose(1, 2))] + self._peer_t:
+            for s, kt, vt in self._block_list(k, v, joint, True):
                 res = sdpa(qt, kt, vt, 0.0, False, False, scale=softmax_scale)
                 outs.append(res[0].transpose(1, 2))
                 lses.append(res[1])
@@ -450,7 +517,7 @@ class _SteadyLayer:
                         from .. import _lib
                         raise RuntimeError("cfx_flag_wait failed: " + (_lib.load().cfx_last_error_string(ctx) or b"").decode())
         else:
-            for s, kk, vv in [(0, k, v)] + self._peers:
+            for s, kk, vv in self._block_list(k, v, joint, False):
                 bo, bl = block_attention(q, kk, vv, 0.0, softmax_scale, causal=False)
                 outs.append(bo)
                 lses.append(bl)

@@ -51,8 +51,16 @@ attention              CFX_ATTENTION                 sdpa | native - who compute
                                                      where they lie (cfx_attn_fwd_blocks: fp16 / bf16, head dim 64 or 128, at most 16 blocks),
                                                      no per-block results and no merge - attn_merge is ignored; on the lane forms the layer's
                                                      chain is issued first and the launch follows stand-alone cfx_flag_wait launches on every
-                                                     peer's flag.  The relay schedule, a layer's first (binding) call, joint tensors, causal,
-                                                     dropout and whatever the launch does not take keep the sdpa path
+                                                     peer's flag.  The relay schedule, a layer's first (binding) call, joint tensors (unless
+                                                     joint="steady", below), causal, dropout and whatever the launch does not take keep the sdpa path
+joint                  CFX_JOINT                     general | steady - where a compact_fwd call WITH joint tensors (joint_tensor_key / _value, strategy front or
+                                                     rear: the text keys of FLUX, SD3, CogVideoX) runs: general (default) = the general path, one
+                                                     block_attention + merge pair per block; steady = the steady layer, once bound, as a call
+                                                     without joint tensors does - attention="sdpa": block 0 attends [joint ; own] (front) or block
+                                                     W-1 [peer ; joint] (rear), merged as attn_merge says; attention="native": ONE launch over
+                                                     [joint, own, peers...] or [own, peers..., joint] with per-block key counts
+                                                     (cfx_attn_fwd_blocks_var, W + 1 <= 16 blocks).  The joint K,V are local to every rank: the
+                                                     exchange and the K,V states are what the general path leaves, bit for bit
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process
 """
@@ -78,6 +86,7 @@ _SETTINGS = {
     "captured_layer": ("CFX_CAPTURED_LAYER", "0", None),
     "attn_merge": ("CFX_ATTN_MERGE", "chain", ("chain", "once")),
     "attention": ("CFX_ATTENTION", "sdpa", ("sdpa", "native")),
+    "joint": ("CFX_JOINT", "general", ("general", "steady")),
 }
 _explicit: Dict[str, str] = {}
 

@@ -811,6 +811,21 @@ int cfx_attn_merge_many(cfx_ctx* ctx, int n, const void* const* block_outs, cons
 #define CFX_ATTN_MAX_BLOCKS 16
 int cfx_attn_fwd_blocks(cfx_ctx* ctx, int n, const void* q, const void* const* ks, const void* const* vs, int B, int Sq, int Sk, int H, int D,
                         float softmax_scale, unsigned flags, void* out, void* lse, void* stream);
+/* cfx_attn_fwd_blocks for K,V blocks of UNEQUAL length: block i is [B][sks[i]][H][D] contiguous (its batch stride is its own), sks a HOST
+ * array of n key counts copied, like the two pointer tables, into the launch's arguments; every other argument is cfx_attn_fwd_blocks's.
+ * What it is for: a layer's joint (text) keys beside its image shards, and queries [text ; image shard] with Sq != sks[i].
+ * The keys of the blocks count as one sequence in table order and the arithmetic is the contract above, rounding by rounding.  Tiles are
+ * 64 keys and never straddle a block: block i has ceil(sks[i] / 64) of them, the launch walks T = sum_i ceil(sks[i] / 64); keys past a
+ * block's OWN end are staged as zeros and scored -inf.  With equal lengths the result is cfx_attn_fwd_blocks's bit for bit; blocks whose
+ * lengths are multiples of 64 give the bits of ONE block that holds their keys in order (the same tile sequence).
+ * Nothing is allocated or written on the device besides out / lse; the launch is capturable and waits for nothing.
+ * `flags`: CFX_ELEM_BF16 only.  Checks, in this order: a NULL pointer - sks and entries of the two tables included - CFX_ERR_NULL; an
+ * unknown flag bit CFX_ERR_CODEC; n outside 1 .. 16, a non-positive B / Sq / H or sks[i], D other than 64 or 128, more workgroups than a
+ * launch takes, a scale that is not finite and positive CFX_ERR_SHAPE; q, out, lse or a block not 16-byte aligned CFX_ERR_ALIGN; a
+ * pending gate error CFX_ERR_GATE.  Each returns before anything is launched.  The launch carries no kernel id: it counts in
+ * cfx_attn_fwd_launches, and cfx_set_attn_qtile sets its query tile too. */
+int cfx_attn_fwd_blocks_var(cfx_ctx* ctx, int n, const void* q, const void* const* ks, const void* const* vs, const int* sks,
+                            int B, int Sq, int H, int D, float softmax_scale, unsigned flags, void* out, void* lse, void* stream);
 int cfx_attn_fwd_launches(cfx_ctx* ctx, unsigned long long* n);
 /* Query rows a workgroup of cfx_attn_fwd_blocks owns: 64, 128 or 256 (2, 4 or 8 waves), 0 = the library's choice (128: measured best on
  * the FLUX shard).  The result is the same function of the inputs whatever the tile; anything else is CFX_ERR_SHAPE.  For
