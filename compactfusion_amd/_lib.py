@@ -176,6 +176,8 @@ SYMBOLS = [
                                           + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_uint] + [ctypes.c_void_p] * 3),
     ("cfx_attn_fwd_blocks_var", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                                ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint] + [ctypes.c_void_p] * 3),
+    ("cfx_attn_fwd_blocks_hd", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                              ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint] + [ctypes.c_void_p] * 3),
     ("cfx_attn_fwd_launches", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]),
     ("cfx_set_attn_qtile", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
 ]

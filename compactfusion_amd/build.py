@@ -25,6 +25,9 @@ ATTN_SRC = [os.path.join(PKG_DIR, "csrc", "cfx_attn.hip")]
 # The same forward for K,V blocks of unequal length (include/cfx.h, cfx_attn_fwd_blocks_var): a list of its own once more -
 # tests/test_attn_fwd_f64.py pins the kernels of ATTN_SRC.
 ATTN_VAR_SRC = [os.path.join(PKG_DIR, "csrc", "cfx_attn_var.hip")]
+# ... and for the head dims between 64 and 128 (include/cfx.h, cfx_attn_fwd_blocks_hd): a list of its own for the same reason -
+# tests/test_attn_var_f64.py pins the kernels of ATTN_VAR_SRC.
+ATTN_HD_SRC = [os.path.join(PKG_DIR, "csrc", "cfx_attn_hd.hip")]
 INC = os.path.join(REPO, "include")
 LIB = os.path.join(PKG_DIR, "libcfx.so")
 LIB_DEV = os.path.join(PKG_DIR, "libcfx_dev.so")      # the same sources with -DCFX_DEV_PROBES (include/cfx_dev.h): tools and one test only
@@ -48,7 +51,7 @@ def needs_build(lib: str = LIB) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = SRC + CAPTURE_SRC + MERGE_SRC + ATTN_SRC + ATTN_VAR_SRC + [os.path.join(INC, "cfx.h"), os.path.join(INC, "cfx_dev.h"), os.path.join(PKG_DIR, "csrc", "cfx_internal.h"),
+    deps = SRC + CAPTURE_SRC + MERGE_SRC + ATTN_SRC + ATTN_VAR_SRC + ATTN_HD_SRC + [os.path.join(INC, "cfx.h"), os.path.join(INC, "cfx_dev.h"), os.path.join(PKG_DIR, "csrc", "cfx_internal.h"),
                   os.path.join(PKG_DIR, "csrc", "cfx_lr.h"), os.path.join(PKG_DIR, "csrc", "cfx_device.h"), os.path.join(PKG_DIR, "csrc", "cfx_host.h"),
                   os.path.join(PKG_DIR, "csrc", "cfx_local.h"), os.path.join(PKG_DIR, "csrc", "cfx_bscale.h")]
     deps += [os.path.join(PKG_DIR, "csrc", h) for h in ("cfx_capture_gate.h", "cfx_topk.h", "cfx_mx.h", "cfx_bblock.h", "cfx_i2block.h", "cfx_i3block.h", "cfx_mxint8.h")]
@@ -62,7 +65,7 @@ def build_lib(force: bool = False, verbose: bool = False, dev_probes: bool = Fal
     lib = LIB_DEV if dev_probes else LIB
     if not force and not needs_build(lib):
         return lib
-    cmd = [hipcc_path()] + HIPCC_FLAGS + (["-DCFX_DEV_PROBES"] if dev_probes else []) + [f"-I{INC}", f"-I{os.path.join(PKG_DIR, 'csrc')}"] + SRC + CAPTURE_SRC + MERGE_SRC + ATTN_SRC + ATTN_VAR_SRC + ["-o", lib + ".tmp"]
+    cmd = [hipcc_path()] + HIPCC_FLAGS + (["-DCFX_DEV_PROBES"] if dev_probes else []) + [f"-I{INC}", f"-I{os.path.join(PKG_DIR, 'csrc')}"] + SRC + CAPTURE_SRC + MERGE_SRC + ATTN_SRC + ATTN_VAR_SRC + ATTN_HD_SRC + ["-o", lib + ".tmp"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     r = subprocess.run(cmd, capture_output=True, text=True)

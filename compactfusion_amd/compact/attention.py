@@ -6,7 +6,8 @@ They are restated here from the published ring-attention algorithm:
     out <- out - sigmoid(lse_b - lse) * (out - out_b) ;  lse <- lse - logsigmoid(lse - lse_b)
 The attention math itself is not part of the compressed-exchange hot path; on the GPU it is PyTorch-ROCm's fused
 SDPA kernel, elsewhere an explicit fp32 softmax.  Opt-in (configure(attention="native")): `attention_blocks`, ONE native launch
-over all of a layer's K,V blocks where they lie (cfx_attn_fwd_blocks) in place of W SDPA calls and their merge."""
+over all of a layer's K,V blocks where they lie (cfx_attn_fwd_blocks; head dims 72 .. 120: cfx_attn_fwd_blocks_hd) in place of W SDPA
+calls and their merge."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -142,9 +143,10 @@ def attention_blocks(q, ks, vs, softmax_scale: Optional[float] = None) -> Tuple[
     """The attention of q (B, Sq, H, D) over ALL the K,V blocks ks[i], vs[i] (B, Sk, H, D) - non-causal, no dropout - as if they were
     one sequence: out (B, Sq, H, D) in q.dtype, lse fp32 as the (B, H, Sq) view of a (B, Sq, H) tensor.  Nothing is concatenated and no
     per-block out / lse exists (include/cfx.h, cfx_attn_fwd_blocks, states the arithmetic rounding by rounding).
-    On the GPU - q and every block fp16 or bf16 alike, contiguous, 16-byte aligned, on one device, D 64 or 128, the blocks agreeing with q
-    in B, H and D - this is ONE native launch: cfx_attn_fwd_blocks for blocks of one shape, cfx_attn_fwd_blocks_var for blocks that
-    differ in their key count (ks[i] (B, Sk_i, H, D)).  The launch takes at most 16 blocks: more on the native path are
+    On the GPU - q and every block fp16 or bf16 alike, contiguous, 16-byte aligned, on one device, D one of ATTN_HEAD_DIMS (64, 128 and
+    the multiples of 8 between them), the blocks agreeing with q in B, H and D - this is ONE native launch: at D 64 or 128
+    cfx_attn_fwd_blocks for blocks of one shape and cfx_attn_fwd_blocks_var for blocks that differ in their key count (ks[i]
+    (B, Sk_i, H, D)); at D 72 .. 120 cfx_attn_fwd_blocks_hd for both.  The launch takes at most 16 blocks: more on the native path are
     REFUSED (ValueError), as `merge_blocks` refuses them.  Anything else (CPU tensors: the host-logic tests; other types, head dims or
     layouts) runs the direct definition in eager fp32 torch."""
     n = len(ks)
@@ -175,9 +177,12 @@ def attention_blocks(q, ks, vs, softmax_scale: Optional[float] = None) -> Tuple[
     return out.transpose(1, 2).contiguous().to(q.dtype), lse.transpose(1, 2)
 
 
+ATTN_HEAD_DIMS = (64, 72, 80, 88, 96, 104, 112, 120, 128)      # 64, 128: cfx_attn_fwd_blocks / _var; between them: cfx_attn_fwd_blocks_hd
+
+
 def attn_native_ok(q, ks, vs) -> bool:
     """whether `attention_blocks` takes (q, ks, vs) to the native launch (the number of blocks aside)"""
-    if not (q.is_cuda and q.dim() == 4 and q.dtype in (torch.float16, torch.bfloat16) and q.shape[-1] in (64, 128)
+    if not (q.is_cuda and q.dim() == 4 and q.dtype in (torch.float16, torch.bfloat16) and q.shape[-1] in ATTN_HEAD_DIMS
             and q.is_contiguous() and q.data_ptr() % 16 == 0 and q.shape[1] > 0):
         return False
     k0 = ks[0]
@@ -188,23 +193,30 @@ def attn_native_ok(q, ks, vs) -> bool:
 
 
 def attn_native_var_ok(q, ks, vs) -> bool:
-    """whether `attention_blocks` takes (q, ks, vs) to the native launch for blocks of unequal length (cfx_attn_fwd_blocks_var; the
-    number of blocks aside): `attn_native_ok`'s conditions block by block - K and V of a block of one shape - with the key count free"""
+    """whether `attention_blocks` takes (q, ks, vs) to the native launch for blocks of unequal length (cfx_attn_fwd_blocks_var, at head
+    dims 72 .. 120 cfx_attn_fwd_blocks_hd; the number of blocks aside): `attn_native_ok`'s conditions block by block - K and V of a block of one shape - with the key count free"""
     return len(ks) == len(vs) and all(k.dim() == 4 and k.shape == v.shape and attn_native_ok(q, (k,), (v,)) for k, v in zip(ks, vs))
 
 
 _attn_fwd_fn = None
 _attn_var_fn = None
+_attn_hd_fn = None
 
 
 def _attn_fwd_native(q, ks, vs, softmax_scale, tabs=None):
     """the launch itself, on arguments `attn_native_ok` passed; `tabs`: the caller's two ctypes pointer tables (compact/ring.py keeps
-    a layer's), built here otherwise"""
+    a layer's), built here otherwise.  A head dim between 64 and 128 goes to cfx_attn_fwd_blocks_hd, which has the unequal-length form
+    only: its key-count table is Sk n times."""
     global _attn_fwd_fn
     import ctypes
     from .. import _lib, codecs
     n = len(ks)
     B, Sq, H, D = q.shape
+    if D not in (64, 128):
+        if tabs is None:
+            P = ctypes.c_void_p * n
+            tabs = P(*[t.data_ptr() for t in ks]), P(*[t.data_ptr() for t in vs])
+        return _attn_fwd_native_var(q, ks, vs, softmax_scale, (tabs[0], tabs[1], (ctypes.c_int * n)(*([ks[0].shape[1]] * n))))
     dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
     if _attn_fwd_fn is None:
         _attn_fwd_fn = _lib.load().cfx_attn_fwd_blocks
@@ -223,30 +235,32 @@ def _attn_fwd_native(q, ks, vs, softmax_scale, tabs=None):
 
 def _attn_fwd_native_var(q, ks, vs, softmax_scale, tabs=None):
     """the launch for blocks of unequal length, on arguments `attn_native_var_ok` passed; `tabs`: the caller's three ctypes tables - K
-    pointers, V pointers, key counts (compact/ring.py keeps a layer's) -, built here otherwise"""
-    global _attn_var_fn
+    pointers, V pointers, key counts (compact/ring.py keeps a layer's) -, built here otherwise.  D 64 or 128: cfx_attn_fwd_blocks_var;
+    a head dim between them: cfx_attn_fwd_blocks_hd, the same arguments"""
+    global _attn_var_fn, _attn_hd_fn
     import ctypes
     from .. import _lib, codecs
     n = len(ks)
     B, Sq, H, D = q.shape
     dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
     if _attn_var_fn is None:
-        _attn_var_fn = _lib.load().cfx_attn_fwd_blocks_var
+        _attn_var_fn, _attn_hd_fn = _lib.load().cfx_attn_fwd_blocks_var, _lib.load().cfx_attn_fwd_blocks_hd
+    fn, name = (_attn_var_fn, "cfx_attn_fwd_blocks_var") if D in (64, 128) else (_attn_hd_fn, "cfx_attn_fwd_blocks_hd")
     if tabs is None:
         P = ctypes.c_void_p * n
         tabs = P(*[t.data_ptr() for t in ks]), P(*[t.data_ptr() for t in vs]), (ctypes.c_int * n)(*[t.shape[1] for t in ks])
     out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Sq, H), dtype=torch.float32, device=q.device)
     ctx = codecs.context(dev)
-    rc = _attn_var_fn(ctx, n, q.data_ptr(), tabs[0], tabs[1], tabs[2], B, Sq, H, D, softmax_scale,
+    rc = fn(ctx, n, q.data_ptr(), tabs[0], tabs[1], tabs[2], B, Sq, H, D, softmax_scale,
                       _lib.ELEM_BF16 if q.dtype == torch.bfloat16 else 0, out.data_ptr(), lse.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        codecs._check(ctx, rc, "cfx_attn_fwd_blocks_var")
+        codecs._check(ctx, rc, name)
     return out, lse.transpose(1, 2)
 
 
 def attn_fwd_launches(device=None) -> int:
-    """cfx_attn_fwd_blocks / cfx_attn_fwd_blocks_var launches enqueued so far on the device's context (the launch carries no kernel id: the context counts)"""
+    """cfx_attn_fwd_blocks / cfx_attn_fwd_blocks_var / cfx_attn_fwd_blocks_hd launches enqueued so far on the device's context (the launch carries no kernel id: the context counts)"""
     import ctypes
     from .. import _lib, codecs
     dev = torch.cuda.current_device() if device is None else (device.index if isinstance(device, torch.device) else device)

@@ -8,14 +8,19 @@ selected by `PatchConfig`:
   sync    - plain all-gather of raw fp16 K and V (the "Patch Parallel" baseline);
   async   - DistriFusion: consume the buffers gathered during the PREVIOUS step (own shard fresh), launch this
             step's gather asynchronously for the next one; the first `async_warmup` steps gather synchronously.
-K and V of a layer travel in ONE collective here (one contiguous [K|V] buffer) instead of two."""
+K and V of a layer travel in ONE collective here (one contiguous [K|V] buffer) instead of two.
+The attention: by default the gathered states are concatenated (twice: K and V; joint tensors twice more) and attended in one SDPA call.
+configure(attention="native") makes it ONE native launch over [joint?] + the per-rank states + [joint?] where they lie, with per-block
+key counts and no torch.cat, in all three modes (`_native_blocks` says when: non-causal, no dropout, no window, at most 16 blocks, and
+a type, layout and head dim - 64, 72, .. 128 - the launch takes); anything else keeps cat + SDPA."""
 from __future__ import annotations
 
 import torch
 import torch.distributed as dist
 
+from ... import config as _settings
 from ...prof import Profiler
-from ..attention import block_attention
+from ..attention import _attn_fwd_native, _attn_fwd_native_var, attn_native_ok, attn_native_var_ok, block_attention
 from ..main import allgather_cache, compact_all_gather_kv, compact_config
 from .df_cache import DummyHandle
 from .df_utils import PatchConfig
@@ -23,10 +28,33 @@ from .df_utils import PatchConfig
 _buffers = {}
 
 
+def _native_blocks(q, ks, vs, joint, jk, jv, dropout_p, causal, window_size):
+    """The K and V block lists of the one-launch attention (configure(attention="native")) - [joint] + ks (front), ks + [joint] (rear),
+    ks - when the launch takes the call: non-causal, no dropout, no window, at most ATTN_MAX_BLOCKS blocks with the joint one, and
+    `attn_native_ok` (blocks of one length) or `attn_native_var_ok` saying yes.  None otherwise: the caller keeps cat + SDPA - never
+    `attention_blocks`' eager definition."""
+    if _settings.get("attention") != "native" or causal or dropout_p != 0 or tuple(window_size) != (-1, -1):
+        return None
+    from ... import _lib
+    lk, lv = list(ks), list(vs)
+    if joint == "front":
+        lk, lv = [jk] + lk, [jv] + lv
+    elif joint == "rear":
+        lk, lv = lk + [jk], lv + [jv]
+    if len(lk) > _lib.ATTN_MAX_BLOCKS or not (attn_native_ok(q, lk, lv) or attn_native_var_ok(q, lk, lv)):
+        return None
+    return lk, lv
+
+
 def _gather_raw_kv(k, v, group, world, key, async_op=False):
     """all-gather [K|V] of every rank into one persistent buffer; returns (handle, k_list, v_list)."""
     n = k.numel()
-    send = torch.cat([k.reshape(-1), v.reshape(-1)])
+    if _settings.get("attention") == "native":     # the same [K|V] buffer without torch.cat: the native path concatenates nothing
+        send = torch.empty(2 * n, dtype=k.dtype, device=k.device)
+        send[:n].copy_(k.reshape(-1))
+        send[n:].copy_(v.reshape(-1))
+    else:
+        send = torch.cat([k.reshape(-1), v.reshape(-1)])
     ent = _buffers.get(key)
     if ent is None or ent.numel() != world * 2 * n or ent.device != k.device:
         ent = torch.empty(world * 2 * n, dtype=k.dtype, device=k.device)
@@ -84,6 +112,11 @@ def patch_gather_fwd(q, k, v, dropout_p=0, softmax_scale=None, causal=True, wind
                 h, nk, nv = _gather_raw_kv(k, v, group, world, ("df", mod_idx, current_iter & 1), async_op=True)
                 cache.put(ck, h, nk + nv, k)
 
+    blocks = _native_blocks(q, ks, vs, joint, joint_tensor_key, joint_tensor_value, dropout_p, causal, window_size)
+    if blocks is not None:                         # configure(attention="native"): ONE launch over the states where they lie, no torch.cat
+        launch = _attn_fwd_native if attn_native_ok(q, *blocks) else _attn_fwd_native_var
+        out, lse = launch(q, blocks[0], blocks[1], softmax_scale)
+        return out, lse, None
     gk = torch.cat(ks, dim=1).contiguous()
     gv = torch.cat(vs, dim=1).contiguous()
     if joint == "front":

@@ -48,18 +48,22 @@ attn_merge             CFX_ATTN_MERGE                chain | once - how a steady
                                                      cfx_flag_wait launches.  The relay schedule and a layer's first (binding) call keep the chain
 attention              CFX_ATTENTION                 sdpa | native - who computes a steady layer's attention in compact_fwd: sdpa (default) = the fused SDPA
                                                      op once per K,V block, merged as attn_merge says; native = ONE launch over all W blocks
-                                                     where they lie (cfx_attn_fwd_blocks: fp16 / bf16, head dim 64 or 128, at most 16 blocks),
+                                                     where they lie (cfx_attn_fwd_blocks: fp16 / bf16, head dim 64 or 128, at most 16 blocks;
+                                                     head dims 72, 80, .. 120 - PixArt's 72, HunyuanDiT's 88 -: cfx_attn_fwd_blocks_hd),
                                                      no per-block results and no merge - attn_merge is ignored; on the lane forms the layer's
                                                      chain is issued first and the launch follows stand-alone cfx_flag_wait launches on every
                                                      peer's flag.  The relay schedule, a layer's first (binding) call, joint tensors (unless
-                                                     joint="steady", below), causal, dropout and whatever the launch does not take keep the sdpa path
+                                                     joint="steady", below), causal, dropout and whatever the launch does not take keep the sdpa path.
+                                                     Patch-parallel (patch_gather_fwd): native = ONE launch over [joint?] + the gathered per-rank
+                                                     K,V states + [joint?] where they lie, no torch.cat; causal, dropout, a window, more than 16
+                                                     blocks and whatever the launch does not take keep the cat + SDPA path
 joint                  CFX_JOINT                     general | steady - where a compact_fwd call WITH joint tensors (joint_tensor_key / _value, strategy front or
                                                      rear: the text keys of FLUX, SD3, CogVideoX) runs: general (default) = the general path, one
                                                      block_attention + merge pair per block; steady = the steady layer, once bound, as a call
                                                      without joint tensors does - attention="sdpa": block 0 attends [joint ; own] (front) or block
                                                      W-1 [peer ; joint] (rear), merged as attn_merge says; attention="native": ONE launch over
                                                      [joint, own, peers...] or [own, peers..., joint] with per-block key counts
-                                                     (cfx_attn_fwd_blocks_var, W + 1 <= 16 blocks).  The joint K,V are local to every rank: the
+                                                     (cfx_attn_fwd_blocks_var, at head dims 72 .. 120 cfx_attn_fwd_blocks_hd; W + 1 <= 16 blocks).  The joint K,V are local to every rank: the
                                                      exchange and the K,V states are what the general path leaves, bit for bit
 hw_queues              GPU_MAX_HW_QUEUES             hardware queues HIP may give its streams - HIP reads it ONCE when it initialises:
                                                      configure(hw_queues=8) must run before the first CUDA call of the process

@@ -826,6 +826,22 @@ int cfx_attn_fwd_blocks(cfx_ctx* ctx, int n, const void* q, const void* const* k
  * cfx_attn_fwd_launches, and cfx_set_attn_qtile sets its query tile too. */
 int cfx_attn_fwd_blocks_var(cfx_ctx* ctx, int n, const void* q, const void* const* ks, const void* const* vs, const int* sks,
                             int B, int Sq, int H, int D, float softmax_scale, unsigned flags, void* out, void* lse, void* stream);
+/* cfx_attn_fwd_blocks_var for the head dims BETWEEN 64 and 128: D = 72, 80, 88, 96, 104, 112 or 120 (PixArt / Latte run heads of 72,
+ * HunyuanDiT of 88).  Every argument and every layout is cfx_attn_fwd_blocks_var's - rows of D elements, no padding: a row is D / 8
+ * 16-byte chunks -; a caller with blocks of one length passes sks[i] = Sk.  The arithmetic is the contract above, rounding by rounding,
+ * with d running over the TRUE D: the launch takes ceil(D / 16) MFMA k-steps to the scores and ceil(D / 32) accumulator blocks to O, and
+ * every operand past column D is an exact zero that is never loaded - a zero product adds nothing to an fp32 sum and rounds nothing.  So
+ * out and lse are, bit for bit, out[..., :D] and lse of cfx_attn_fwd_blocks_var on q and the blocks zero-padded to D = 128 with the same
+ * softmax_scale.  Nothing within or past a row is read beyond its D elements.  Tiles, masking, the walk's order: cfx_attn_fwd_blocks_var's.
+ * Nothing is allocated or written on the device besides out / lse; the launch is capturable and waits for nothing.
+ * `flags`: CFX_ELEM_BF16 only.  Checks, in cfx_attn_fwd_blocks_var's order: a NULL pointer - sks and entries of the two tables included -
+ * CFX_ERR_NULL; an unknown flag bit CFX_ERR_CODEC; n outside 1 .. 16, a non-positive B / Sq / H or sks[i], D other than the seven above
+ * (64 and 128 included: they are cfx_attn_fwd_blocks_var's), more workgroups than a launch takes, a scale that is not finite and
+ * positive CFX_ERR_SHAPE; q, out, lse or a block not 16-byte aligned CFX_ERR_ALIGN; a pending gate error CFX_ERR_GATE.  Each returns
+ * before anything is launched.  The launch carries no kernel id: it counts in cfx_attn_fwd_launches, and cfx_set_attn_qtile sets its
+ * query tile too (the same bits whatever the tile). */
+int cfx_attn_fwd_blocks_hd(cfx_ctx* ctx, int n, const void* q, const void* const* ks, const void* const* vs, const int* sks,
+                           int B, int Sq, int H, int D, float softmax_scale, unsigned flags, void* out, void* lse, void* stream);
 int cfx_attn_fwd_launches(cfx_ctx* ctx, unsigned long long* n);
 /* Query rows a workgroup of cfx_attn_fwd_blocks owns: 64, 128 or 256 (2, 4 or 8 waves), 0 = the library's choice (128: measured best on
  * the FLUX shard).  The result is the same function of the inputs whatever the tile; anything else is CFX_ERR_SHAPE.  For
